@@ -13,6 +13,11 @@ the result D2H run on a side stream, double-buffered, so that they overlap the k
 results left in HBM (what rounds 1-3 reported as `value`).
 
 Prints ONE JSON line (rank 0).  PyTorch is plumbing only (device tensors, streams, torch.distributed).
+
+A plain run measures the headline only: set-up, warm-up, the --steps timed batches of the path `value` is quoted on, the
+result line.  `--full` adds everything else, as before: the device-resident leg next to the host-inclusive one, the handles
+leg, the roofline and per-kernel figures, the oracle comparison of a read sample and the CPU baseline.  `--dump-outputs DIR`
+writes the complete results of a fixed, seeded sample of the last timed batch's reads as DIR/<field>.npy (float64).
 """
 import argparse
 import ctypes as C
@@ -28,11 +33,54 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
-HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0        # MI355X HBM3E: 8.0 TB/s spec
+DUMP_READS = 16384           # --dump-outputs: reads of the last timed batch whose results are written (fewer if over DUMP_MAX_BYTES)
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SEED = 20240504
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, headers, stream, n_reads, labeled):
+    """--dump-outputs: a fixed, seeded sample of one batch's reads, their raw result records (`headers`: n_reads x 64 bytes,
+    `stream`: the used 32-bit words, host arrays) decoded as a caller decodes them (mgx_results_from_raw), one float64 array per
+    field: per read its index in the batch, status and first alignment (aln_begin), per alignment its scalars, and the
+    concatenated node ids, CIGAR runs, path spellings (character codes) and, label-aware, label ids."""
+    from metagraph_amd import capi
+    lib = capi.lib()
+    os.makedirs(out_dir, exist_ok=True)
+    draw = np.random.default_rng(DUMP_SEED).choice(n_reads, min(n_reads, DUMP_READS), replace=False)
+    words = np.ascontiguousarray(stream).view(np.uint32)
+    while True:
+        idx = np.sort(draw)
+        hdr = np.ascontiguousarray(headers.reshape(n_reads, -1)[idx])
+        store, res = C.c_void_p(), capi.Results()
+        rc = lib.mgx_results_from_raw_labeled(hdr.ctypes.data, len(idx), words.ctypes.data, len(words), int(labeled),
+                                              C.byref(store), C.byref(res))
+        assert rc == 0, lib.mgx_last_error()
+        try:
+            a = capi.results_arrays(res)
+            alns = a["alns"]
+            arrays = {"read_index": idx, "status": a["status"], "aln_begin": a["aln_begin"]}
+            for f in ("score", "offset", "clipping", "end_clipping", "num_matches", "n_nodes", "n_cigar", "seq_len", "orientation"):
+                arrays["aln_" + f] = alns[f]
+            arrays.update({"nodes": a["nodes"], "cigar_len": a["cigar"]["len"], "cigar_op": a["cigar"]["op"], "seqs": a["seqs"]})
+            if labeled:
+                arrays["aln_n_labels"] = alns["n_labels"]
+                n_lab = int(alns["n_labels"].sum()) if len(alns) else 0
+                arrays["labels"] = np.ctypeslib.as_array(res.labels, shape=(n_lab,)) if n_lab else np.zeros(0, np.uint32)
+            arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}       # (node ids < 2^53: exact)
+        finally:
+            lib.mgx_raw_store_free(store)
+        total = sum(v.nbytes for v in arrays.values())
+        if total <= DUMP_MAX_BYTES or len(draw) == 1:
+            break
+        draw = draw[:len(draw) // 2]
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log("outputs: %d reads of the last timed batch, %d arrays, %.1f MB -> %s" % (len(idx), len(arrays), total / 1e6, out_dir))
 
 
 def main():
@@ -61,6 +109,11 @@ def main():
     ap.add_argument("--handles", type=int, default=int(os.environ.get("MGX_BENCH_HANDLES", 1)), help="(measurement) a further leg with this many "
                     "aligner handles on streams of their own, one host thread each, the --steps batches dealt round robin — what "
                     "`metagraph align -p N` does on one device (cli/align.cpp:440-475): the kernels of neighbouring batches overlap")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the device-resident leg, the handles leg, the roofline "
+                    "and per-kernel figures, the oracle comparison and the CPU baseline (the options above that steer them act "
+                    "only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the complete results of a "
+                    "fixed, seeded sample of the last timed batch's reads as DIR/<field>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
     if args.host_steps < 0:
         args.host_steps = args.steps
@@ -196,30 +249,37 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    for _ in range(args.warmup):
+    # The device-resident leg is the headline with --host-steps 0 and a further figure with --full; a plain run warms up on it
+    # all the same (at least one batch: the host pipeline below sizes its pinned result buffers from a batch's output).
+    device_leg = args.full or args.host_steps == 0
+    for _ in range(args.warmup if device_leg else max(1, args.warmup)):
         step()
     sync()
-    t1 = time.time()
-    align_ms, map_ms = [], []
-    for _ in range(args.steps):
-        step()
-        st = A.stats()
-        align_ms.append(st["align_kernel_ms"])
-        map_ms.append(st["seed_kernel_ms"])
-    sync()
-    elapsed = time.time() - t1
-    if dist:
-        tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed = float(tmax.item())
-    st = A.stats()
-    ms_per_step = 1000.0 * elapsed / max(1, args.steps)
     total_reads = args.reads * world
-    value = total_reads / (elapsed / max(1, args.steps))
+    align_ms, map_ms, value, ms_per_step = [], [], None, None
+    if device_leg:
+        t1 = time.time()
+        for _ in range(args.steps):
+            step()
+            st = A.stats()
+            align_ms.append(st["align_kernel_ms"])
+            map_ms.append(st["seed_kernel_ms"])
+        sync()
+        elapsed = time.time() - t1
+        if dist:
+            tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed = float(tmax.item())
+        st = A.stats()
+        ms_per_step = 1000.0 * elapsed / max(1, args.steps)
+        value = total_reads / (elapsed / max(1, args.steps))
+        if args.dump_outputs and args.host_steps == 0 and rank == 0:
+            hd, sd, u = mg.device_result_tensors(A, dev)
+            dump_outputs(args.dump_outputs, hd.cpu().numpy(), sd[:4 * u].cpu().numpy(), args.reads, AN is not None)
 
     # ---------------- (measurement) several handles at work on the device at once ----------------
     handles_ms = None
-    if args.handles > 1 and not dist:
+    if args.full and args.handles > 1 and not dist:
         import ctypes as _ct
         import threading
         L = capi.lib()
@@ -284,6 +344,7 @@ def main():
             return ev
 
         def host_pipeline(n_steps):
+            """-> (pinned buffer pair, used stream words) holding the last batch's results"""
             up = upload(0)
             down_done = [None, None]
             for i in range(n_steps):
@@ -309,11 +370,12 @@ def main():
                     mg.gather_device_results(A, dist, rank, world, dev)
                 up = nxt
             side.synchronize()
+            return i % 2, u
 
         host_pipeline(1)
         sync()
         th = time.time()
-        host_pipeline(args.host_steps)
+        last_slot, last_used = host_pipeline(args.host_steps)
         sync()
         eh = time.time() - th
         if dist:
@@ -322,12 +384,44 @@ def main():
             eh = float(tmax.item())
         host_ms = 1000.0 * eh / args.host_steps
         host_value = total_reads / (eh / args.host_steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, hdr_h[last_slot].numpy(), stream_h[last_slot][:4 * last_used].numpy(), args.reads, AN is not None)
         del reads_h, offsets_h, hdr_h, stream_h, rbuf, obuf
+        if not device_leg:
+            st = A.stats()
 
     if rank != 0:
         if dist:
             dist.barrier()
             dist.destroy_process_group()
+        return
+
+    # `value`: SURVEY 8(d) — host buffers in, host buffers out (the pipelined run above); with --full the device-resident rate next to it
+    out = {"metric": "aligned reads/sec (150 bp, k=31)", "value": round(host_value if host_value else value, 1), "unit": "reads/s",
+           "value_is": "host-inclusive (read H2D + result D2H overlapped with the kernels)" if host_value else "device-resident (--host-steps 0)"}
+    if value is not None:
+        out.update({"value_device_resident": round(value, 1), "ms_per_step_device_resident": round(ms_per_step, 3)})
+    out.update({"n_gpus": world, "steps": args.host_steps if host_value else args.steps, "warmup": args.warmup,
+                "ms_per_step": round(host_ms if host_value else ms_per_step, 3),
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+                "config": {"workload": "%d synthetic %d bp reads per GPU vs %d-edge k=%d BOSS graph (%.0f Mbp iid genome + %d SNP windows%s), CLI-default scoring" %
+                           (args.reads, args.read_len, n_edges, args.k, args.genome / 1e6, args.snps,
+                            ("; PRIMARY mode through the CanonicalDBG wrapper" if args.graph_mode == "primary" else "")
+                            + ("; label-aware (LabeledAligner) with a %d-label annotation, one label per genome segment" % args.labels if args.labels else "")),
+                           "reads_per_gpu": args.reads, "graph_edges": n_edges, "k": args.k, "graph_mode": args.graph_mode,
+                           "parallelism": "reads sharded x%d, graph replicated" % world},
+                "full": args.full})
+
+    def finish(out):
+        print(json.dumps(out), flush=True)
+        # a batch that lost alignments to a capacity limit is not a valid measurement
+        assert st["n_capacity_errors"] == 0, "%d reads ended with a capacity status" % st["n_capacity_errors"]
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(out)
         return
 
     # ---------------- roofline of the dominant kernel (HIP events inside libmgx, per launch) ----------
@@ -542,19 +636,7 @@ def main():
                    "extrapolated_whole_socket": {"cores": 128, "value": round(one * 128, 1),
                                                  "note": "single-thread rate x 128 physical cores (2 x EPYC 9575F); not measured"}}
 
-    # `value`: SURVEY 8(d) — host buffers in, host buffers out (the pipelined run above); the device-resident rate next to it
-    out = {"metric": "aligned reads/sec (150 bp, k=31)", "value": round(host_value if host_value else value, 1), "unit": "reads/s",
-           "value_is": "host-inclusive (read H2D + result D2H overlapped with the kernels)" if host_value else "device-resident (--host-steps 0)",
-           "value_device_resident": round(value, 1), "ms_per_step_device_resident": round(ms_per_step, 3),
-           "n_gpus": world, "steps": args.host_steps if host_value else args.steps, "warmup": args.warmup,
-           "ms_per_step": round(host_ms if host_value else ms_per_step, 3),
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
-           "config": {"workload": "%d synthetic %d bp reads per GPU vs %d-edge k=%d BOSS graph (%.0f Mbp iid genome + %d SNP windows%s), CLI-default scoring" %
-                      (args.reads, args.read_len, n_edges, args.k, args.genome / 1e6, args.snps,
-                       ("; PRIMARY mode through the CanonicalDBG wrapper" if args.graph_mode == "primary" else "")
-                       + ("; label-aware (LabeledAligner) with a %d-label annotation, one label per genome segment" % args.labels if args.labels else "")),
-                      "reads_per_gpu": args.reads, "graph_edges": n_edges, "k": args.k, "graph_mode": args.graph_mode, "parallelism": "reads sharded x%d, graph replicated" % world},
-           "roofline": roofline, "cpu_baseline": cpu, "parity": parity}
+    out.update({"roofline": roofline, "cpu_baseline": cpu, "parity": parity})
     if handles_ms is not None:
         out["handles_leg"] = {"handles": args.handles, "ms_per_step": round(handles_ms, 3), "value": round(args.reads / (handles_ms * 1e-3), 1),
                               "note": "device-resident reads, --steps batches dealt to the handles' host threads; measurement only"}
@@ -565,12 +647,7 @@ def main():
     roofline["step_algorithmic_bytes"] = round(step_bytes)
     roofline["step_achieved"] = round(step_bytes / (step_ms * 1e-3) / 1e9, 2) if step_ms > 0 else 0.0
     roofline["step_frac"] = round(roofline["step_achieved"] / HBM_PEAK_GBS, 5)
-    print(json.dumps(out), flush=True)
-    # a batch that lost alignments to a capacity limit is not a valid measurement
-    assert st["n_capacity_errors"] == 0, "%d reads ended with a capacity status" % st["n_capacity_errors"]
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":
