@@ -321,11 +321,15 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   ext64=0|1|2          small batches on the one-read-per-wavefront 64-lane kernel (default 1) or on the 8-lane groups;
  *                        label-aware aligners: 2 = every batch on the 64-lane labeled kernel
  *   groups_per_wave=n    8-lane kernel: n = 1 .. 8 groups of a wavefront take reads, 0 = all (default: from the batch size)
- *   multi_pass=0|1       one extension per read and launch (default: automatic from the seeds per read); two_pass=1
+ *   multi_pass=0|1       one extension per read and launch (default: automatic from the seeds per read)
  *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic)
  *   device_share=n       n handles are at work on this device at the same time (worker threads): this handle sizes its per-slot
  *                        arenas for 1 / n of the machine (default 1: all of it)
- *   no_compact / no_alias / no_bt_runs / no_flat / primary_alt_build = 1   A/B forms of the column records and loops
+ *   seed_lane=0|1        the lane-per-read seeder in front of the seeding kernel (default: automatic)
+ *   seed_wps=4|8         wavefronts per SIMD of the short-read seeding kernel (default 8)
+ *   map_pipe=0|1|2       the mapping kernel as a request / response machine: never / from 65536 chains on (default) / always
+ *   retry_capacity=0     capacity statuses are handed to the caller instead of re-aligning those queries with larger limits
+ *   no_compact / no_alias / no_bt_runs / no_flat = 1   A/B forms of the column records and loops
  * Unknown name: MGX_ERR_INVALID.  (Measurement probes that change results or occupancy exist only in -DMGX_PROBES builds.) */
 int mgx_aligner_set_pipeline(mgx_aligner *a, const char *name);
 /* The HIP stream (a hipStream_t, passed as void * so that this header needs no HIP header) every kernel launch, asynchronous

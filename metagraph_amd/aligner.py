@@ -228,8 +228,9 @@ class Aligner:
         return out
 
     def set_pipeline(self, name):
-        """Kernel selection: 'split8' (the pipeline), 'general' / 'chain' (extension chain path off / on), 'key=value'
-        options (include/mgx.h, mgx_aligner_set_pipeline); results never depend on it."""
+        """Kernel selection: 'split8' (the name of the one pipeline: accepted, selects nothing), 'general' / 'chain'
+        (extension chain path off / on), 'key=value' options (include/mgx.h lists them at mgx_aligner_set_pipeline);
+        results never depend on it.  Anything else raises MgxError(MGX_ERR_INVALID)."""
         L = capi.lib()
         L.mgx_aligner_set_pipeline.argtypes = [C.c_void_p, C.c_char_p]
         _check(L.mgx_aligner_set_pipeline(self.h, name.encode()))

@@ -1,0 +1,66 @@
+// kernel_units.hpp — what the translation units of libmgx.so call in one another: the launchers and build constants of the
+// kernel units (the host driver in mgx.hip launches them) and the library-internal accessors of mgx_annot.hip.  Declarations
+// only.  mgx.hip includes this file and so does every unit that defines one of these symbols, so that a signature which
+// drifts on one side is a compile error instead of a call through a wrong prototype.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+// The launchers take their parameter block as `const void *` (every kernel unit instantiates the shared sources in a namespace of
+// its own, so the struct types differ by name from unit to unit).  The blocks are the same plain data everywhere: each unit
+// asserts the size of its own instantiation against these, next to the cast.
+constexpr size_t MGX_ALIGN_PARAMS_BYTES = 728;          // sizeof(AlignParams), align_types.hpp
+constexpr size_t MGX_LANE_PARAMS_BYTES = 848;           // sizeof(LaneParams), lane_types.hpp
+constexpr size_t MGX_SEED_LANE_PARAMS_BYTES = 824;      // sizeof(SeedLaneParams), seed_lane.hpp
+
+struct mgx_annotation;
+
+extern "C" {
+
+// mgx.hip: the thread-local message behind mgx_last_error(), for the other units' failures
+void mgx_set_last_error(const char *msg);
+
+// mgx_grp.hip (MGX_GROUP = 8), four builds whose names differ by a suffix: the product, `_prim` (the product with the CanonicalDBG
+// branches: PRIMARY graphs), `_alt` (room for MGX_MAX_ALTERNATIVE_PATHS alignments per query, either kind of graph) and `_lab`
+// (the label-aware extender).  params: AlignParams (host memory); n_groups = arena slices; lds_bytes = dynamic LDS per group;
+// phase = PH_EXTEND (the only half instantiated for sub-wave groups).
+#define MGX_DECLARE_GRP8_BUILD(sfx)                                                                                          \
+    int mgx_launch_align_grp8##sfx(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream);      \
+    int mgx_grp_waves_per_simd8##sfx(void);                                                                                  \
+    unsigned mgx_grp_static_lds8##sfx(void);
+MGX_DECLARE_GRP8_BUILD()
+MGX_DECLARE_GRP8_BUILD(_prim)
+MGX_DECLARE_GRP8_BUILD(_alt)
+MGX_DECLARE_GRP8_BUILD(_lab)
+#undef MGX_DECLARE_GRP8_BUILD
+int mgx_grp_max_alt8_lab(void);
+
+// mgx_ext64.hip / mgx_lab64.hip: the extension half with all 64 lanes on one read, plain and label-aware.  params: AlignParams
+// (host memory); blocks = wavefronts; lds_bytes = dynamic LDS per wavefront.
+int mgx_launch_ext64(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream);
+unsigned mgx_ext64_static_lds(void);
+int mgx_ext64_waves_per_simd(void);
+int mgx_launch_lab64(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream);
+unsigned mgx_lab64_static_lds(void);
+int mgx_lab64_waves_per_simd(void);
+int mgx_lab64_max_alt(void);
+
+// mgx_primary.hip: the seeding kernel with the CanonicalDBG branches; wps8 selects the 8-waves-per-SIMD instantiation
+int mgx_launch_seed_primary(const void *params, uint32_t blocks, uint32_t lds_bytes, int wps8, void *stream);
+
+// mgx_lane.hip: the lane-per-read kernel.  d_params: LaneParams in DEVICE memory; blocks = resident wavefronts
+int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream);
+int mgx_lane_waves_per_simd(void);
+
+// mgx_seedlane.hip: the lane-per-read seeder.  d_params: SeedLaneParams in DEVICE memory; long_reads: the build for reads of
+// more than SL_SHORT_L characters
+int mgx_launch_seed_lane(const void *d_params, uint32_t blocks, int long_reads, void *stream);
+int mgx_seed_lane_waves_per_simd(void);
+
+// mgx_annot.hip: the matrix as the label-aware extension kernels read it (AlignParams::anno_*), and the annotation's
+// process-unique id
+void mgx_annotation_device_view(const mgx_annotation *a, int *device, uint64_t *n_rows, const uint64_t **head,
+                                const uint32_t **count, const uint32_t **more);
+uint64_t mgx_annotation_uid(const mgx_annotation *a);
+
+}  // extern "C"

@@ -25,8 +25,11 @@
 #include "chain_host.hpp"
 #include "lane_types.hpp"
 #include "seed_lane.hpp"
+#include "kernel_units.hpp"
 
 using namespace mgx;
+static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES && sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES
+              && sizeof(SeedLaneParams) == MGX_SEED_LANE_PARAMS_BYTES, "a parameter block differs from what the kernel units take");
 
 // =================================================================================================
 // kernels
@@ -449,59 +452,51 @@ struct mgx_graph {
     mutable std::map<uint64_t, bool> dummy_clean;   // per annotation, by its process-unique id (mgx_annotation_uid: never reused, unlike the handle's address)
 };
 
-extern "C" int mgx_launch_align_grp8(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream);    // mgx_grp.hip, MGX_GROUP=8
-extern "C" int mgx_grp_waves_per_simd8(void);
-extern "C" unsigned mgx_grp_static_lds8(void);
-// the seeding kernel with the CanonicalDBG branches (mgx_primary.hip); wps8 selects the 8-waves-per-SIMD instantiation
-extern "C" int mgx_launch_seed_primary(const void *params, uint32_t blocks, uint32_t lds_bytes, int wps8, void *stream);
-// the same kernel with room for MGX_MAX_ALTERNATIVE_PATHS alignments per query (num_alternative_paths > 1) and with the
-// CanonicalDBG branches (PRIMARY graphs)
-extern "C" int mgx_launch_align_grp8_alt(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream);
-extern "C" unsigned mgx_grp_static_lds8_alt(void);
-extern "C" int mgx_grp_waves_per_simd8_alt(void);
-extern "C" int mgx_launch_ext64(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream);      // mgx_ext64.hip
-extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream);                         // mgx_lane.hip
-extern "C" int mgx_launch_seed_lane(const void *d_params, uint32_t blocks, int long_reads, void *stream);                    // mgx_seedlane.hip
-extern "C" int mgx_seed_lane_waves_per_simd(void);
-// the 64-lane extension kernel with the label-aware extender compiled in (mgx_lab64.hip: -DMGX_WITH_LABELS=1)
-extern "C" int mgx_launch_align_grp8_lab(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream);   // mgx_grp.hip, the labeled build
-extern "C" unsigned mgx_grp_static_lds8_lab(void);
-extern "C" int mgx_grp_waves_per_simd8_lab(void);
-extern "C" int mgx_grp_max_alt8_lab(void);
-extern "C" int mgx_launch_lab64(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream);
-extern "C" unsigned mgx_lab64_static_lds(void);
-extern "C" int mgx_lab64_waves_per_simd(void);
-extern "C" int mgx_lab64_max_alt(void);
-extern "C" void mgx_annotation_device_view(const mgx_annotation *a, int *device, uint64_t *n_rows, const uint64_t **head,
-                                           const uint32_t **count, const uint32_t **more);                    // mgx_annot.hip
-extern "C" uint64_t mgx_annotation_uid(const mgx_annotation *a);                                            // mgx_annot.hip
-extern "C" int mgx_annotation_has_coordinates(const mgx_annotation *a);                                     // mgx_annot.hip
-extern "C" int mgx_lane_waves_per_simd(void);
-// (measurement builds only, tools/build_lane_short_variant.sh: the kernel's -DMGX_LANE_SHORT build — reads of up to 160 characters,
-// three wavefronts per SIMD; profiles/r06_ab10_lane_three_waves.txt is why the product does not carry it)
-#ifdef MGX_WITH_LANE_SHORT
-extern "C" int mgx_launch_lane_short(const void *d_params, uint32_t blocks, void *stream);                   // mgx_lane.hip, -DMGX_LANE_SHORT
-extern "C" int mgx_lane_short_waves_per_simd(void);
-#else
-static int mgx_launch_lane_short(const void *, uint32_t, void *) { return (int)hipErrorNotSupported; }
-static int mgx_lane_short_waves_per_simd(void) { return 0; }
-#endif
-extern "C" unsigned mgx_ext64_static_lds(void);
-extern "C" int mgx_ext64_waves_per_simd(void);
-extern "C" int mgx_launch_align_grp8_prim(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream);
-extern "C" unsigned mgx_grp_static_lds8_prim(void);
-extern "C" int mgx_grp_waves_per_simd8_prim(void);
+// The pipeline run_align launches ("split8", the only one): seeding — the lane-per-read seeder, then one wavefront per read
+// (k_align<PH_SEED>) on what it left —, a radix sort of the reads by predicted extension work, extension — the lane-per-read
+// kernel, then 8-lane groups (8 reads per wavefront, mgx_grp.hip) or one read per wavefront on what it left.
 
-// The pipeline run_align launches: seeding by one wavefront per read (k_align<PH_SEED>), a radix sort of the reads by
-// predicted extension work, extension by 8-lane groups (8 reads per wavefront, mgx_grp.hip).  (Round 1 also carried
-// fused and 16- / 64- / 1-lane instantiations for A/B measurements; they are gone.)
-enum AlignMode { MODE_SPLIT8 = 4, MODE_BAD = -1 };
+// launches of the counted extension kernels since the library was loaded (mgx_kernel_launch_counts; bit order of MGX_KERNEL_*)
+enum LaunchCounter { CNT_NONE = -1, CNT_GRP8 = 0, CNT_GRP8_PRIM, CNT_GRP8_ALT, CNT_EXT64, CNT_LANE, CNT_N };
+static std::atomic<uint64_t> g_kernel_launches[CNT_N];
 
-// launches of every extension kernel since the library was loaded (mgx_kernel_launch_counts; bit order of MGX_KERNEL_*)
-static std::atomic<uint64_t> g_kernel_launches[5];
+// The builds of the extension kernel (kernel_units.hpp).  Slot sizing and the launch read the same row.
+struct ExtBuild {
+    int (*launch_grp)(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream);     // 8 reads per wavefront ...
+    int (*launch_64)(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream);                   // ... or one (the other is null)
+    int (*waves_per_simd)(void);
+    unsigned (*static_lds)(void);
+    uint64_t kernel_bit;              // MGX_KERNEL_*
+    LaunchCounter counter;            // its entry of g_kernel_launches (the label-aware builds are not counted)
+};
+enum ExtBuildId { EXT_GRP8, EXT_GRP8_PRIM, EXT_GRP8_ALT, EXT_GRP8_LAB, EXT_EXT64, EXT_LAB64 };
+static const ExtBuild g_ext_builds[] = {
+    { mgx_launch_align_grp8, nullptr, mgx_grp_waves_per_simd8, mgx_grp_static_lds8, MGX_KERNEL_GRP8, CNT_GRP8 },
+    { mgx_launch_align_grp8_prim, nullptr, mgx_grp_waves_per_simd8_prim, mgx_grp_static_lds8_prim, MGX_KERNEL_GRP8_PRIM, CNT_GRP8_PRIM },
+    { mgx_launch_align_grp8_alt, nullptr, mgx_grp_waves_per_simd8_alt, mgx_grp_static_lds8_alt, MGX_KERNEL_GRP8_ALT, CNT_GRP8_ALT },
+    { mgx_launch_align_grp8_lab, nullptr, mgx_grp_waves_per_simd8_lab, mgx_grp_static_lds8_lab, MGX_KERNEL_GRP8_LAB, CNT_NONE },
+    { nullptr, mgx_launch_ext64, mgx_ext64_waves_per_simd, mgx_ext64_static_lds, MGX_KERNEL_EXT64, CNT_EXT64 },
+    { nullptr, mgx_launch_lab64, mgx_lab64_waves_per_simd, mgx_lab64_static_lds, MGX_KERNEL_LAB64, CNT_NONE },
+};
+static uint32_t waves_per_cu(const ExtBuild &b) { return 4u * (uint32_t)b.waves_per_simd(); }
+// The 8-lane-group build a configuration extends on: the label-aware one; else the one with room for alternative paths
+// (either kind of graph); else, on PRIMARY graphs, the product with the CanonicalDBG branches; else the product.
+static const ExtBuild &group_build(bool labeled, bool primary, uint64_t agg_cap) {
+    return g_ext_builds[labeled ? EXT_GRP8_LAB : agg_cap > 1 ? EXT_GRP8_ALT : primary ? EXT_GRP8_PRIM : EXT_GRP8];
+}
 
-// Measurement probes (occupancy scans, LDS caps, ablations that give WRONG results) exist only in -DMGX_PROBES builds
-// (tools/build_variant.sh); the product library ignores their environment variables.
+// Latency-critical scalar arrays go to LDS when they fit next to the other resident wavefronts of the CU.  The budget: a
+// wavefront's share of the CU's 160 KB minus the kernel's static LDS and a margin (overshooting by a few bytes costs a whole
+// resident wavefront per CU); the dynamic LDS per read: what its arrays want (fast_lds_bytes) or its share of the budget.
+static uint32_t lds_budget(uint32_t waves_cu, uint32_t static_lds, uint32_t margin) { return (160u * 1024u) / waves_cu - static_lds - margin; }
+static uint32_t lds_per_read(uint32_t Lmax, uint32_t waves_cu, uint32_t static_lds, uint32_t margin, uint32_t reads_per_wave = 1) {
+    return std::min<uint32_t>(fast_lds_bytes(Lmax), lds_budget(waves_cu, static_lds, margin) / reads_per_wave) & ~15u;
+}
+
+// Environment variables: every read of the environment in this unit goes through this block.
+// (a) Measurement probes — occupancy scans, LDS caps, prints, ablations that give WRONG results — are read in -DMGX_PROBES builds
+// (tools/build_variant.sh) only; the product library ignores them: MGX_MAP_BYTES, MGX_DEBUG_SLOTS, MGX_ABLATE,
+// MGX_EXT_GROUPS_PCT, MGX_EXT_LDS_CAP, MGX_SEED_LDS_CAP, MGX_SEED_LDS_PRINT, MGX_SEED_WAVES_PCT, MGX_HOST_TIMERS.
 #ifdef MGX_PROBES
 static bool probe_env_set(const char *name) { const char *e = getenv(name); return e && *e && strcmp(e, "0") != 0; }
 static uint32_t probe_env_u32(const char *name, uint32_t dflt) { const char *e = getenv(name); return e ? (uint32_t)atoi(e) : dflt; }
@@ -511,12 +506,46 @@ static inline bool probe_env_set(const char *) { return false; }
 static inline uint32_t probe_env_u32(const char *, uint32_t dflt) { return dflt; }
 static inline uint32_t probe_env_pct(const char *) { return 100u; }
 #endif
-static AlignMode parse_mode(const char *e) {
-    if (!e) return MODE_BAD;
-    if (!strcmp(e, "split8")) return MODE_SPLIT8;
-    return MODE_BAD;
+// (b) Read by the product library too (the tools/pmc_*.sh flows and the variant builds run against it); none changes a result:
+//   MGX_PREFIX_LEN_MAX=m    graph load: the suffix-range table covers at most m characters (2 .. 15)
+//   MGX_PRIMARY_TABLES=0    graph load: no reverse-complement tables for a PRIMARY graph
+//   MGX_LANE_HASH_MULT=f    k_lane: f times the node-table slots per lane
+//   MGX_LANE_BLOCKS_PCT=p   k_lane: p % of the resident wavefronts (is the kernel bound by the latency of its own dependent
+//                           accesses, or by what the memory system serves per second?)
+//   MGX_LANE_TIMERS / MGX_SL_TIMERS   print the section timers of a -DMGX_LANE_TIMERS / -DMGX_SL_TIMERS build of the lane kernels
+static bool env_int(const char *name, int *v) {
+    const char *e = getenv(name);
+    if (e) *v = atoi(e);
+    return e != nullptr;
 }
-static AlignMode default_mode() { return MODE_SPLIT8; }
+
+// The words of mgx_aligner::cursors (16 x 8 B): what the kernels count, through the pointers the host hands them.
+enum CursorSlot {
+    CUR_OUT = 0,              // output-stream words handed out (keeps counting past the capacity: mgx_align_batch_device)
+    CUR_READ = 1,             // next work item of a persistent kernel: rewound before every launch that takes items from it
+    CUR_SEED = 2,             // seeds in the seed stream (keeps counting past the capacity)
+    CUR_LMAX = CUR_SEED,      // ... and, while a batch is staged, the length of its longest read (k_kmer_counts)
+    CUR_RETRY = 3,            // multi-pass extension: reads listed for the next pass (CUR_OUT .. CUR_RETRY: cleared when run_align starts)
+    CUR_MAP = 4,              // next chain of the mapping kernels
+    CUR_LANE_BAIL = 5,        // k_lane: reads passed on to the extension kernel ...
+    CUR_LANE_DONE = 6,        // ... and reads finished (the host reads the two with one copy)
+    CUR_SL_BAIL = 8,          // lane-per-read seeder, first pass: reads left, listed from the front ...
+    CUR_SL_DONE = 9,          // (both passes: reads seeded)
+    CUR_SL_BAIL2 = 10,        // second pass: reads left for the wave-per-read seeding kernel
+    CUR_SL_BAIL_BACK = 11,    // ... first pass: reads left, listed from the back
+    CUR_WORDS = 16
+};
+
+// mgx_aligner::ev: the stream positions mgx_stats' times are measured between (collect_stats)
+enum AlignEvent {
+    EV_MAP_BEGIN, EV_MAP_END,         // run_map
+    EV_ALIGN_BEGIN, EV_ALIGN_END,     // run_align, from the first seeding launch
+    EV_SEEDED,                        // both seeders are through
+    EV_SORTED,                        // the work sort is through: the extension starts
+    EV_LANE_END,                      // the lane-per-read kernel is through (= the extension's start when it does not run)
+    EV_SEED_LANE_END,                 // the lane-per-read seeder is through
+    EV_COUNT
+};
 
 struct mgx_aligner {
     const mgx_graph *graph = nullptr;
@@ -531,7 +560,7 @@ struct mgx_aligner {
     DevBuf rng_fwd, rng_rc;       // and the (rl, ru) of matches >= min_seed_length (8 B per position; optional)
     bool have_rng = false;
     DevBuf score_matrix, seqs, offsets, counts, node_begin, nodes_fwd, nodes_rc, arena, results, stream, cursors, d_stats, d_stats_map, scan_tmp, dbg_seeds;
-    DevBuf seed_hdr, seed_stream, work_key, work_key_sorted, order_in, order, sort_tmp, retry_list;    // split pipeline
+    DevBuf seed_hdr, seed_stream, work_key, work_key_sorted, order_in, order, sort_tmp, retry_list;    // seeds from the seeding to the extension kernels, the work sort
     DevBuf resume_pool[2], retry_list2, retry_key[2];      // multi-pass extension: resume records, retry lists and keys (ping-pong)
     DevBuf lane_scratch, lane_params, lane_bail, lane_hist;           // lane-per-read kernel: per-lane scratch, its parameter block, the reads it passes on
     bool packed_valid = false;    // pk_* / iv_* hold this batch's strands (k <= 32 and the batch was mapped)
@@ -568,11 +597,9 @@ struct mgx_aligner {
                                                  // capacity retry read the batch back only while it is still the staged one
     std::vector<uint64_t> m_node_begin, m_fwd, m_rc;
     mgx_stats hstats;
-    hipEvent_t ev[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };     // ([7]: the lane-per-read seeder is through)
-    bool split_ran = false;
+    hipEvent_t ev[EV_COUNT] = {};
     uint64_t kernels_ran = 0;     // MGX_KERNEL_* bits of the extension kernels the last batch launched
     uint64_t seed_scale = 1, seed_cap = 0;
-    AlignMode mode = default_mode();
     uint64_t arena_stride = 0;
     uint64_t out_words = 0;       // capacity of `stream` for the current batch shape
     uint64_t out_min_words = 0;   // raised when a batch overflowed the heuristic size
@@ -584,11 +611,8 @@ struct mgx_aligner {
         int ext64 = 1;            // 0: never the 64-lane one-read-per-wavefront kernel (small batches run the 8-lane groups)
         int groups_per_wave = -1; // 0 = all 8 groups of a wavefront take reads, 1 .. 8 = that many
         int multi_pass = -1;      // multi-pass extension on / off
-        int two_pass = 0;
         int no_compact = 0, no_alias = 0, no_bt_runs = 0, no_flat = 0;
-        int primary_alt_build = 0;
         int lane = -1;            // the lane-per-read kernel in front of the extension kernel: -1 auto, 0 off, 1 forced
-        int lane_short = 0;       // (measurement builds with MGX_WITH_LANE_SHORT) 1: batches whose longest read has <= 160 characters run the lane kernel's three-wavefront build
         int seed_lane = -1;       // the lane-per-read seeder in front of the seeding kernel (seed_lane.hpp): -1 auto, 0 off, 1 forced
         int seed_wps = 8;         // wavefronts per SIMD of the short-read seeding kernel: 8 (64 VGPRs, spills) or 4 (102 VGPRs, tables in LDS)
         int device_share = 1;     // handles expected to run on this device at the same time (worker threads, -p N): the per-slot
@@ -597,6 +621,12 @@ struct mgx_aligner {
                                   // 0 = never (one chain step per lane and iteration: rounds 1-4)
     } opt;
 };
+
+static unsigned long long *cursor(const mgx_aligner *A, CursorSlot s) { return A->cursors.as<unsigned long long>() + s; }
+// zero the slots first .. last
+static hipError_t clear_cursors(mgx_aligner *A, CursorSlot first, CursorSlot last) {
+    return hipMemsetAsync(cursor(A, first), 0, (size_t)(last - first + 1) * 8, A->hstream);
+}
 
 extern "C" {
 
@@ -795,7 +825,7 @@ int mgx_graph_create(const mgx_boss_view *view, int device, mgx_graph **out) {
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
             while (cap_m < 15 && (8ull << (2 * (cap_m + 1))) <= free_b / 16) ++cap_m;
         }
-        if (const char *e = getenv("MGX_PREFIX_LEN_MAX")) cap_m = (uint32_t)std::min(15, std::max(2, atoi(e)));
+        if (int e; env_int("MGX_PREFIX_LEN_MAX", &e)) cap_m = (uint32_t)std::min(15, std::max(2, e));
         const uint32_t m = choose_prefix_len(n, g.k, cap_m);
         DevBuf key;
         if (int rc = key.ensure((n + 1) * 4)) return rc;
@@ -823,7 +853,9 @@ int mgx_graph_create(const mgx_boss_view *view, int device, mgx_graph **out) {
     // (PRIMARY graphs: terminus | terminus of the ids v + n | palindrome bits | rc_node table — canon_graph.hpp primary_tables().
     // MGX_PRIMARY_TABLES=0 leaves the last two out (4 bytes per BOSS node less) and the wrapper re-derives spellings and look-ups
     // per expansion: same results, ~7x the random lines)
-    G->primary_tables = G->mode == MGX_MODE_PRIMARY && !(getenv("MGX_PRIMARY_TABLES") && atoi(getenv("MGX_PRIMARY_TABLES")) == 0);
+    int primary_tables = 1;
+    env_int("MGX_PRIMARY_TABLES", &primary_tables);
+    G->primary_tables = G->mode == MGX_MODE_PRIMARY && primary_tables != 0;
     const size_t terminus_bytes = G->mode != MGX_MODE_PRIMARY ? (size_t)n_blocks * 8
                                   : (size_t)n_blocks * 8 * 3 + (G->primary_tables ? (size_t)(tot[5] + 2) * 4 : 0);
     if (int rc = G->terminus.ensure(terminus_bytes, true)) return rc;
@@ -929,7 +961,7 @@ static int aligner_create(const mgx_graph *g, const mgx_config *config, const mg
     }
     if (int rc = A->score_matrix.ensure(128 * 128)) return rc;
     HIP_TRY(hipMemcpy(A->score_matrix.p, c.score_matrix, 128 * 128, hipMemcpyHostToDevice));
-    if (int rc = A->cursors.ensure(128)) return rc;
+    if (int rc = A->cursors.ensure(CUR_WORDS * 8)) return rc;
     if (int rc = A->d_stats.ensure(sizeof(KernelStats))) return rc;
     if (int rc = A->d_stats_map.ensure(sizeof(KernelStats))) return rc;
     for (auto &e : A->ev) HIP_TRY(hipEventCreate(&e));
@@ -993,9 +1025,8 @@ static int stage_batch(mgx_aligner *A, const char *seqs, const uint64_t *offsets
     }
     if (int rc = A->counts.ensure((n + 2) * 8)) return rc;
     if (int rc = A->node_begin.ensure((n + 2) * 8)) return rc;
-    unsigned long long *cur = A->cursors.as<unsigned long long>();
-    HIP_TRY(hipMemsetAsync(cur, 0, 128, A->hstream));
-    k_kmer_counts<<<(uint32_t)((n + 1 + 255) / 256), 256, 0, A->hstream>>>(*d_offsets, n, k, A->counts.as<uint64_t>(), cur + 2);
+    HIP_TRY(hipMemsetAsync(A->cursors.p, 0, CUR_WORDS * 8, A->hstream));
+    k_kmer_counts<<<(uint32_t)((n + 1 + 255) / 256), 256, 0, A->hstream>>>(*d_offsets, n, k, A->counts.as<uint64_t>(), cursor(A, CUR_LMAX));
     HIP_TRY(hipGetLastError());
     size_t tmp_bytes = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, A->counts.as<uint64_t>(), A->node_begin.as<uint64_t>(), (int)(n + 1), A->hstream));
@@ -1004,7 +1035,7 @@ static int stage_batch(mgx_aligner *A, const char *seqs, const uint64_t *offsets
     uint64_t total_kmers = 0;
     unsigned long long lmax = 0;
     HIP_TRY(copy_sync(A, &total_kmers, A->node_begin.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(copy_sync(A, &lmax, cur + 2, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(A, &lmax, cursor(A, CUR_LMAX), 8, hipMemcpyDeviceToHost));
     A->total_kmers = total_kmers;
     A->n_reads = n;
     *Lmax_out = (uint32_t)lmax;
@@ -1040,11 +1071,11 @@ static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets
         HIP_TRY(hipMemsetAsync(A->mlen_rc.p, 0xFF, A->total_kmers + 1, A->hstream));
         return MGX_OK;
     }
-    unsigned long long *map_cursor = A->cursors.as<unsigned long long>() + 4;
-    HIP_TRY(hipMemsetAsync(map_cursor, 0, 8, A->hstream));
+    unsigned long long *map_cursor = cursor(A, CUR_MAP);
+    HIP_TRY(clear_cursors(A, CUR_MAP, CUR_MAP));
     HIP_TRY(hipMemsetAsync(A->mlen_fwd.p, 0xFF, A->total_kmers + 1, A->hstream));       // MLEN_UNKNOWN
     if (do_rc) HIP_TRY(hipMemsetAsync(A->mlen_rc.p, 0xFF, A->total_kmers + 1, A->hstream));
-    HIP_TRY(hipEventRecord(A->ev[0], A->hstream));
+    HIP_TRY(hipEventRecord(A->ev[EV_MAP_BEGIN], A->hstream));
     {
         // persistent lanes: enough wavefronts to fill the device, never more lanes than chains
         hipDeviceProp_t prop;
@@ -1102,7 +1133,7 @@ static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets
                                                                              A->nodes_fwd.as<uint32_t>(), A->nodes_rc.as<uint32_t>(), n);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(A->ev[1], A->hstream));
+    HIP_TRY(hipEventRecord(A->ev[EV_MAP_END], A->hstream));
     return MGX_OK;
 }
 
@@ -1113,61 +1144,71 @@ static int work_key_bits(uint64_t n) {
     return std::min(b, 32);
 }
 
-static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax) {
-    {
-        std::string err;
-        int rc = derive_limits(A->cfg, A->have_user_lim ? &A->user_lim : nullptr, Lmax, &A->lim, &err, A->anno != nullptr, A->label_scale);
-        if (rc) return fail(rc, "%s", err.c_str());
-    }
-    const bool labeled = A->anno != nullptr;
-    const DevLimits &l = A->lim;
-    const uint64_t stride = arena_bytes(l);
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, A->graph->device));
-    // The lane-per-read kernel (mgx_lane.hip) in front of the group kernel: does this batch's configuration qualify?  Its
-    // scratch is taken before the arena is sized from what is free.
+// ------------------------------------------------------------------------------------------------
+// run_align: one staged and mapped batch through seeding, the work sort and extension
+// ------------------------------------------------------------------------------------------------
+// What the stages of run_align hand to one another (the limits of the batch are A->lim).
+struct AlignPlan {
+    uint64_t n = 0;                   // reads
+    bool labeled = false;
+    uint32_t cus = 0;                 // compute units of the device
+    bool lane_ok = false;             // the lane-per-read kernel takes this batch's configuration (and got its scratch)
+    uint32_t lane_blocks = 0;         // its resident wavefronts
     LaneParams LP;
+    uint64_t agg_cap = 1;             // alignments kept per query
+    const ExtBuild *grp = nullptr;    // the 8-lane-group build the configuration extends on (group_build)
+    uint64_t wave_slots = 0;          // resident wavefronts of the seeding kernel (one per read)
+    uint64_t stride = 0, slots = 0;   // the arena: bytes per slice, slices
+    size_t sort_tmp_bytes = 0;
+    AlignParams P;
+};
+
+// The lane-per-read kernel (mgx_lane.hip) in front of the group kernel: does this batch's configuration qualify?  Its scratch
+// is taken before the arena is sized from what is free.
+static int plan_lane(mgx_aligner *A, AlignPlan &pl) {
+    const DevLimits &l = A->lim;
+    LaneParams &LP = pl.LP;
     memset(&LP, 0, sizeof(LP));
     std::string lane_why;
-    // (two builds of the kernel: reads of up to 160 characters at three wavefronts per SIMD, up to 256 at two)
-    const bool lane_short = A->opt.lane_short != 0 && l.Lmax <= 160 && mgx_lane_short_waves_per_simd() > 0;
-    const uint32_t lane_blocks = (uint32_t)prop.multiProcessorCount * 4u * (uint32_t)(lane_short ? mgx_lane_short_waves_per_simd() : mgx_lane_waves_per_simd());
+    pl.lane_blocks = pl.cus * 4u * (uint32_t)mgx_lane_waves_per_simd();
     // (label-aware batches, round 6: the lane takes the reads whose seeds and columns all carry one and the same single label —
     // lane_read.hpp; it needs the annotation's "no dummy node's row holds a label" flag, as it reads rows without the W test)
-    bool lane_ok = A->opt.lane != 0 && A->packed_valid && A->mode == MODE_SPLIT8 && !A->opt.two_pass && A->opt.multi_pass != 1
-                   && lane_enabled(A->cfg, A->dcfg, A->graph->g.k, l.Lmax, A->no_fast, &LP, &lane_why,
-                                   labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u)
-                   && (A->opt.lane == 1 || n >= (uint64_t)lane_blocks * 16);       // (a small batch: the spread / 64-lane kernels are quicker)
-    if (lane_ok) {
-        LP.max_cols = lane_max_cols(l.Lmax, A->dcfg.xdrop);
-        LP.hash_slots = next_pow2(2ull * LP.max_cols);
-        if (const char *hm = getenv("MGX_LANE_HASH_MULT")) LP.hash_slots *= (uint32_t)std::max(1, atoi(hm));      // (measurement only)
-        LP.rest_stride = (lane_rest_bytes(LP.max_cols, LP.hash_slots) + 63) & ~63ull;
-        LP.wave_stride = lane_wave_scratch_bytes(LP.max_cols, LP.rest_stride);
-        const size_t before = A->lane_scratch.bytes;
-        if (A->lane_scratch.ensure((size_t)lane_blocks * LP.wave_stride, true) != MGX_OK) lane_ok = false;      // (no room: the group kernel alone)
-        else if (A->lane_scratch.bytes != before) HIP_TRY(hipMemsetAsync(A->lane_scratch.p, 0, A->lane_scratch.bytes, A->hstream));    // node tables start empty
-    }
+    pl.lane_ok = A->opt.lane != 0 && A->packed_valid && A->opt.multi_pass != 1
+                 && lane_enabled(A->cfg, A->dcfg, A->graph->g.k, l.Lmax, A->no_fast, &LP, &lane_why,
+                                 pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u)
+                 && (A->opt.lane == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16);       // (a small batch: the spread / 64-lane kernels are quicker)
+    if (!pl.lane_ok) return MGX_OK;
+    LP.max_cols = lane_max_cols(l.Lmax, A->dcfg.xdrop);
+    LP.hash_slots = next_pow2(2ull * LP.max_cols);
+    if (int hm; env_int("MGX_LANE_HASH_MULT", &hm)) LP.hash_slots *= (uint32_t)std::max(1, hm);
+    LP.rest_stride = (lane_rest_bytes(LP.max_cols, LP.hash_slots) + 63) & ~63ull;
+    LP.wave_stride = lane_wave_scratch_bytes(LP.max_cols, LP.rest_stride);
+    const size_t before = A->lane_scratch.bytes;
+    if (A->lane_scratch.ensure((size_t)pl.lane_blocks * LP.wave_stride, true) != MGX_OK) pl.lane_ok = false;      // (no room: the group kernel alone)
+    else if (A->lane_scratch.bytes != before) HIP_TRY(hipMemsetAsync(A->lane_scratch.p, 0, A->lane_scratch.bytes, A->hstream));    // node tables start empty
+    return MGX_OK;
+}
+
+// How many reads are in flight at once (slots), each with a slice of the arena: as many as the kernels keep resident, or as
+// the free memory holds.
+static int size_arena(mgx_aligner *A, AlignPlan &pl) {
+    const DevLimits &l = A->lim;
+    const uint64_t n = pl.n, stride = arena_bytes(l);
+    pl.stride = stride;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const AlignMode mode = A->mode;
-    const bool split = mode == MODE_SPLIT8;      // always
-    const uint64_t wave_slots = (uint64_t)prop.multiProcessorCount * 4 * MGX_ALIGN_WAVES_PER_SIMD;   // seeding kernel: one wavefront per read
-    // (the extension kernel that will run: the same alt / prim selection as launch_groups below)
-    const bool sel_primary = A->dcfg.canonical >= 2;
+    pl.wave_slots = (uint64_t)pl.cus * 4 * MGX_ALIGN_WAVES_PER_SIMD;
     // (post_chain_alignments keeps up to MGX_MAX_ALTERNATIVE_PATHS alignments per query: the build with room for them)
-    const uint64_t agg_cap = std::max<uint64_t>(1, A->cfg.post_chain_alignments ? (uint64_t)post_chain_capacity(A->cfg.num_alternative_paths) : A->cfg.num_alternative_paths);
-    const bool sel_alt = agg_cap > 1 || (sel_primary && A->opt.primary_alt_build == 1);
-    const uint64_t ext_wps = sel_alt ? mgx_grp_waves_per_simd8_alt() : sel_primary ? mgx_grp_waves_per_simd8_prim() : mgx_grp_waves_per_simd8();
-    // (label-aware batches: seeding as ever, extension on the one-read-per-wavefront labeled kernel)
-    const uint64_t want_slots = labeled ? std::max<uint64_t>(wave_slots, (uint64_t)prop.multiProcessorCount * 4 * 8 * mgx_grp_waves_per_simd8_lab())
-                                        : std::max<uint64_t>(split ? wave_slots : 0, (uint64_t)prop.multiProcessorCount * 4 * 8 * ext_wps);
+    pl.agg_cap = std::max<uint64_t>(1, A->cfg.post_chain_alignments ? (uint64_t)post_chain_capacity(A->cfg.num_alternative_paths) : A->cfg.num_alternative_paths);
+    pl.grp = &group_build(pl.labeled, A->dcfg.canonical >= 2, pl.agg_cap);
+    // (label-aware batches: seeding as ever, extension on the labeled builds)
+    const uint64_t want_slots = std::max<uint64_t>(pl.wave_slots, (uint64_t)pl.cus * waves_per_cu(*pl.grp) * 8);
     // The arena gets what is free after the buffers this stage allocates AFTER it (result records, output stream, seed
     // stream, sort arrays: estimated generously) and a margin; buffers kept from an earlier batch are already outside
     // `free_b`.  (Half of the free memory, as before, left 15 % of the extension kernel's groups without a slice at
     // 10 M reads next to a host framework's cached allocations.)
     const uint64_t later = n * (sizeof(ReadResult) + sizeof(SeedHdr) + 24 + 16)
-                           + (n * (((uint64_t)l.Lmax + l.Lmax / 4 + 40) * agg_cap) + 1024) * 4
+                           + (n * (((uint64_t)l.Lmax + l.Lmax / 4 + 40) * pl.agg_cap) + 1024) * 4
                            + (n * 24 + A->total_kmers / 8 + 4096) * A->seed_scale * sizeof(DevSeed) + (1ull << 30);
     const uint64_t held = A->results.bytes + A->stream.bytes + A->seed_stream.bytes + A->seed_hdr.bytes;     // re-used as far as they reach
     const uint64_t need_later = later > held ? later - held : 0;
@@ -1180,38 +1221,61 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     budget /= share;
     uint64_t slots = std::min<uint64_t>(std::min<uint64_t>((want_slots + share - 1) / share, std::max<uint64_t>(n, 1)), std::max<uint64_t>(1, budget / stride));
     if (slots == 0) slots = 1;
-    {
-        // The hash tables of the convergence checker are cleared by generation tags that persist in each slice,
-        // so a slice only needs zeroing when its layout (stride) changes or the buffer is new.
-        const size_t before = A->arena.bytes;
-        if (int rc = A->arena.ensure(slots * stride, true)) return rc;
-        if (A->arena.bytes != before || A->arena_stride != stride) {
-            HIP_TRY(hipMemsetAsync(A->arena.p, 0, A->arena.bytes, A->hstream));
-            A->arena_stride = stride;
-        }
+    // The hash tables of the convergence checker are cleared by generation tags that persist in each slice,
+    // so a slice only needs zeroing when its layout (stride) changes or the buffer is new.
+    const size_t before = A->arena.bytes;
+    if (int rc = A->arena.ensure(slots * stride, true)) return rc;
+    if (A->arena.bytes != before || A->arena_stride != stride) {
+        HIP_TRY(hipMemsetAsync(A->arena.p, 0, A->arena.bytes, A->hstream));
+        A->arena_stride = stride;
     }
+    pl.slots = slots;
     A->n_slots = (uint32_t)slots;
     if (probe_env_set("MGX_DEBUG_SLOTS")) fprintf(stderr, "run_align: n %llu stride %llu want_slots %llu slots %llu free %.1f GB\n", (unsigned long long)n, (unsigned long long)stride, (unsigned long long)want_slots, (unsigned long long)slots, free_b / 1e9);
+    return MGX_OK;
+}
+
+// Result records, output stream, seed stream and sort arrays of the batch; the cursors and counters of this run start at zero.
+static int size_buffers(mgx_aligner *A, AlignPlan &pl) {
+    const DevLimits &l = A->lim;
+    const uint64_t n = pl.n;
     if (int rc = A->results.ensure(n * sizeof(ReadResult))) return rc;
-    uint64_t words_per_read = ((uint64_t)l.Lmax + l.Lmax / 4 + 40) * agg_cap;
-    if (labeled) words_per_read = words_per_read * 2 + 16;      // (an alignment per label group + the label lists; heuristic as below)
+    uint64_t words_per_read = ((uint64_t)l.Lmax + l.Lmax / 4 + 40) * pl.agg_cap;
+    if (pl.labeled) words_per_read = words_per_read * 2 + 16;      // (an alignment per label group + the label lists; heuristic as below)
     // heuristic size (one alignment per read: nodes + CIGAR runs + path characters); a batch that needs more is re-run
     // with what it asked for (mgx_align_batch_device), so the size is never a correctness limit
-    uint64_t out_words = std::max<uint64_t>(n * words_per_read + 1024, A->out_min_words);
-    if (int rc = A->stream.ensure(out_words * 4)) return rc;
-    A->out_words = out_words;
+    A->out_words = std::max<uint64_t>(n * words_per_read + 1024, A->out_min_words);
+    if (int rc = A->stream.ensure(A->out_words * 4)) return rc;
     if (A->keep_seeds) {
         if (int rc = A->dbg_seeds.ensure(n * 2 * (uint64_t)l.max_seeds * sizeof(DevSeed))) return rc;
         HIP_TRY(hipMemsetAsync(A->dbg_seeds.p, 0, n * 2 * (uint64_t)l.max_seeds * sizeof(DevSeed), A->hstream));
     }
-    unsigned long long *cur = A->cursors.as<unsigned long long>();
-    HIP_TRY(hipMemsetAsync(cur, 0, 32, A->hstream));
+    HIP_TRY(clear_cursors(A, CUR_OUT, CUR_RETRY));
     HIP_TRY(hipMemsetAsync(A->d_stats.p, 0, sizeof(KernelStats), A->hstream));     // counters of this run of the stage only
-    AlignParams P;
+    // Seeds travel from the seeding kernels to the extension kernels through a compact stream.  Typical reads carry a handful
+    // of seeds; long or repetitive ones scale with their k-mer count.  The stream is sized by a heuristic times A->seed_scale;
+    // mgx_align_batch_device re-runs the stage with a larger scale if the seeding kernel ran out of room (the cursor keeps
+    // counting), so the size is never a correctness limit.
+    A->seed_cap = std::min<uint64_t>(n * 2 * (uint64_t)l.max_seeds, (n * 24 + A->total_kmers / 8 + 4096) * A->seed_scale);
+    if (int rc = A->seed_hdr.ensure(n * sizeof(SeedHdr))) return rc;
+    if (int rc = A->seed_stream.ensure(A->seed_cap * sizeof(DevSeed))) return rc;
+    if (int rc = A->work_key.ensure(n * 4)) return rc;
+    if (int rc = A->work_key_sorted.ensure(n * 4)) return rc;
+    if (int rc = A->order_in.ensure(n * 4)) return rc;
+    if (int rc = A->order.ensure(n * 4)) return rc;
+    if (int rc = A->retry_list.ensure(n * 4 + 4)) return rc;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, pl.sort_tmp_bytes, A->work_key.as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
+                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, work_key_bits(n), A->hstream));
+    return A->sort_tmp.ensure(pl.sort_tmp_bytes);
+}
+
+// the kernels' parameter block (host side only: every buffer it points to exists by now)
+static void fill_params(mgx_aligner *A, AlignPlan &pl, const char *d_seqs, const uint64_t *d_offsets) {
+    AlignParams &P = pl.P;
     memset(&P, 0, sizeof(P));
     P.g = A->graph->g;
     P.cfg = A->dcfg;
-    P.lim = l;
+    P.lim = A->lim;
     P.score_matrix = A->score_matrix.as<int8_t>();
     P.seqs = d_seqs;
     P.offsets = d_offsets;
@@ -1222,14 +1286,14 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     P.mlen_rc = A->mlen_rc.as<uint8_t>();
     P.rng_fwd = A->have_rng ? A->rng_fwd.as<uint2>() : nullptr;
     P.rng_rc = A->have_rng ? A->rng_rc.as<uint2>() : nullptr;
-    P.n_reads = n;
+    P.n_reads = pl.n;
     P.arena = A->arena.as<uint8_t>();
-    P.arena_stride = stride;
+    P.arena_stride = pl.stride;
     P.results = A->results.as<ReadResult>();
     P.out_stream = A->stream.as<uint32_t>();
-    P.out_capacity = out_words;
-    P.out_cursor = cur;
-    P.read_cursor = cur + 1;
+    P.out_capacity = A->out_words;
+    P.out_cursor = cursor(A, CUR_OUT);
+    P.read_cursor = cursor(A, CUR_READ);
     P.stats = A->d_stats.as<KernelStats>();
     P.dbg_seeds = A->keep_seeds ? A->dbg_seeds.as<DevSeed>() : nullptr;
     P.no_fast = A->no_fast;
@@ -1241,336 +1305,337 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     P.no_alias = A->opt.no_alias != 0;
     P.no_bt_runs = A->opt.no_bt_runs != 0;
     P.no_flat = A->opt.no_flat != 0 || A->cfg.post_chain_alignments;       // (the flat group loop is the one-alignment-per-query driver)
-    if (labeled) {
+    if (pl.labeled) {
         int adev = 0;
         mgx_annotation_device_view(A->anno, &adev, &P.anno_rows, &P.anno_head, &P.anno_count, &P.anno_more);
         P.labeled = 1u | (A->anno_dummy_clean ? 2u : 0u);
         P.anno_base = A->graph->mode == MGX_MODE_CANONICAL ? A->graph->canon_repr.as<uint32_t>() : nullptr;
         P.no_alias = 1;           // (a flush clears columns in place: convergence entries must not alias their S windows)
     }
-#ifdef MGX_PROBES
-    P.ablate = getenv("MGX_ABLATE") ? (uint32_t)atoi(getenv("MGX_ABLATE")) : 0u;      // timing probes: WRONG results (probe builds only)
-#endif
-    size_t sort_tmp_bytes = 0;
-    if (split) {
-        // seeds travel from the seeding kernel to the extension kernel through a compact stream
-        // typical reads carry a handful of seeds; long or repetitive ones scale with their k-mer count.  The stream is
-        // sized by a heuristic times A->seed_scale; mgx_align_batch_device re-runs the stage with a larger scale if the
-        // seeding kernel ran out of room (the cursor keeps counting), so the size is never a correctness limit.
-        const uint64_t seed_cap = std::min<uint64_t>(n * 2 * (uint64_t)l.max_seeds,
-                                                     (n * 24 + A->total_kmers / 8 + 4096) * A->seed_scale);
-        A->seed_cap = seed_cap;
-        if (int rc = A->seed_hdr.ensure(n * sizeof(SeedHdr))) return rc;
-        if (int rc = A->seed_stream.ensure(seed_cap * sizeof(DevSeed))) return rc;
-        if (int rc = A->work_key.ensure(n * 4)) return rc;
-        if (int rc = A->work_key_sorted.ensure(n * 4)) return rc;
-        if (int rc = A->order_in.ensure(n * 4)) return rc;
-        if (int rc = A->order.ensure(n * 4)) return rc;
-        if (int rc = A->retry_list.ensure(n * 4 + 4)) return rc;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp_bytes, A->work_key.as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
-                                                   A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, work_key_bits(n), A->hstream));
-        if (int rc = A->sort_tmp.ensure(sort_tmp_bytes)) return rc;
-        P.seed_hdr = A->seed_hdr.as<SeedHdr>();
-        P.seed_stream = A->seed_stream.as<DevSeed>();
-        P.seed_capacity = seed_cap;
-        P.seed_cursor = cur + 2;
-        P.work_key = A->work_key.as<uint32_t>();
+    P.ablate = probe_env_u32("MGX_ABLATE", 0u);      // timing probes: WRONG results (probe builds only)
+    P.seed_hdr = A->seed_hdr.as<SeedHdr>();
+    P.seed_stream = A->seed_stream.as<DevSeed>();
+    P.seed_capacity = A->seed_cap;
+    P.seed_cursor = cursor(A, CUR_SEED);
+    P.work_key = A->work_key.as<uint32_t>();
+}
+
+// The lane-per-read seeder (seed_lane.hpp, mgx_seedlane.hip) first: every lane seeds its own read and either publishes
+// header, seeds and work key as the seeding kernel would, or lists the read for a second pass with bigger buffers; what that
+// leaves is listed for the seeding kernel, which then seeds the list from scratch (no host round trip in between: the lists'
+// lengths stay on the device).
+static int seed_by_lanes(mgx_aligner *A, AlignPlan &pl) {
+    const DevLimits &l = A->lim;
+    AlignParams &P = pl.P;
+    const uint64_t n = pl.n;
+    const bool seed_lane = A->opt.seed_lane != 0 && A->packed_valid && P.pkw[0] && P.ivw[0]
+                           && (!A->dcfg.fwd_and_rc || (P.pkw[1] && P.ivw[1])) && P.mlen_fwd && P.rng_fwd
+                           && (!A->dcfg.fwd_and_rc || (P.mlen_rc && P.rng_rc))
+                           && seed_lane_enabled(A->dcfg, (uint32_t)A->graph->g.k, l.Lmax, true, true)
+                           && (A->opt.seed_lane == 1 || n >= 4096);
+    if (!seed_lane || !n) return MGX_OK;
+    const bool long_reads = l.Lmax > (uint32_t)SL_SHORT_L;            // (the kernel's build with nine packed words per strand)
+    const uint32_t resident = pl.cus * 4 * (uint32_t)mgx_seed_lane_waves_per_simd();
+    const uint32_t blocks1 = (uint32_t)std::min<uint64_t>(resident, (n + 63) / 64);
+    // (the second pass: what the first left — a sixth of a typical batch — with the big buffers)
+    const uint32_t blocks2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident / (long_reads ? 2 : 1), (n / 4 + 63) / 64));
+    const bool many = (uint64_t)A->graph->g.k >= A->dcfg.max_seed_length;
+    const uint32_t me1 = many ? (long_reads ? SL_SEEDS_1_MANY_LONG : SL_SEEDS_1_MANY) : SL_SEEDS_1, mp1 = many ? SL_PENDING_1_MANY : SL_PENDING_1;
+    const uint32_t me2 = long_reads ? SL_SEEDS_2_LONG : SL_SEEDS_2, mp2 = long_reads ? SL_PENDING_2_LONG : SL_PENDING_2;
+    const uint64_t words1 = seed_lane_wave_scratch_words(me1, mp1), words2 = seed_lane_wave_scratch_words(me2, mp2);
+    if (int rc = A->seedlane_scratch.ensure((size_t)std::max<uint64_t>(blocks1 * words1, blocks2 * words2) * 4)) return rc;
+    if (int rc = A->seedlane_params.ensure(2 * sizeof(SeedLaneParams))) return rc;
+    if (int rc = A->seedlane_bail.ensure(2 * (n * 4 + 4))) return rc;
+    if (int rc = A->seedlane_hist.ensure(32 * 8)) return rc;          // ([16 .. 24): section timers of -DMGX_SL_TIMERS builds)
+    HIP_TRY(hipMemsetAsync(A->seedlane_hist.p, 0, 32 * 8, A->hstream));
+    HIP_TRY(clear_cursors(A, CUR_SL_BAIL, CUR_SL_BAIL_BACK));
+    SeedLaneParams SP[2];
+    memset(SP, 0, sizeof(SP));
+    uint32_t *list1 = A->seedlane_bail.as<uint32_t>(), *list2 = list1 + n + 1;
+    for (int ps = 0; ps < 2; ++ps) {
+        SP[ps].P = P;
+        SP[ps].P.n_items = n;
+        SP[ps].scratch = A->seedlane_scratch.as<uint32_t>();
+        SP[ps].long_reads = long_reads ? 1u : 0u;
+        SP[ps].second_pass = (uint32_t)ps;
+        SP[ps].list_len = n;
+        SP[ps].done_count = cursor(A, CUR_SL_DONE);
     }
-    HIP_TRY(hipEventRecord(A->ev[2], A->hstream));
-    // latency-critical scalar arrays go to LDS when they fit next to the other resident waves of the CU
-    // per-wavefront share of the CU's 160 KB minus the kernel's static LDS (control block, sdust scratch, score rows);
-    // overshooting by a few bytes costs a whole resident wavefront per CU
-    // (the seeding kernels: control block + the interval lists of the sdust scratch; no score rows — seed_kernel.hpp)
+    // first pass: every read; what it leaves goes to list1 from both ends
+    SP[0].max_entries = me1; SP[0].max_pending = mp1;
+    SP[0].bail_list = list1; SP[0].bail_count = cursor(A, CUR_SL_BAIL); SP[0].bail_count_back = cursor(A, CUR_SL_BAIL_BACK);
+    // second pass: list1; what it leaves goes to list2 (why a read left is counted where it leaves for the wave program)
+    SP[1].max_entries = me2; SP[1].max_pending = mp2;
+    SP[1].in_list = list1; SP[1].in_count = cursor(A, CUR_SL_BAIL); SP[1].in_count_back = cursor(A, CUR_SL_BAIL_BACK);
+    SP[1].bail_list = list2; SP[1].bail_count = cursor(A, CUR_SL_BAIL2);
+    SP[1].bail_hist = A->seedlane_hist.as<unsigned long long>();
+    HIP_TRY(copy_sync(A, A->seedlane_params.p, SP, sizeof(SP), hipMemcpyHostToDevice));
+    if (int rc = mgx_launch_seed_lane(A->seedlane_params.p, blocks1, long_reads, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane-per-read seeder: %d", rc);
+    HIP_TRY(clear_cursors(A, CUR_READ, CUR_READ));
+    if (int rc = mgx_launch_seed_lane(A->seedlane_params.as<SeedLaneParams>() + 1, blocks2, long_reads, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane-per-read seeder, second pass: %d", rc);
+    HIP_TRY(clear_cursors(A, CUR_READ, CUR_READ));
+    P.seed_list = list2;
+    P.n_items_ptr = cursor(A, CUR_SL_BAIL2);
+    A->seedlane_launched = 1;
+    return MGX_OK;
+}
+
+// The seeding kernel, one wavefront per read, on every read or on what the lane-per-read seeder listed: the instantiation at
+// 8 wavefronts per SIMD for short reads on a full machine, else the one at MGX_ALIGN_WAVES_PER_SIMD; PRIMARY graphs: the
+// builds with the CanonicalDBG branches (mgx_primary.hip).
+static int seed_by_waves(mgx_aligner *A, AlignPlan &pl) {
+    const DevLimits &l = A->lim;
+    AlignParams &P = pl.P;
+    const bool primary = A->dcfg.canonical >= 2;
+    // (static LDS of the seeding kernels: control block + the interval lists of the sdust scratch; no score rows — seed_kernel.hpp)
     const uint32_t static_lds = (uint32_t)((sizeof(Wave) + SDUST_LDS_BYTES_REGTAB + 16 + 127) & ~127ull);
-    uint32_t lds_budget = (160u * 1024u) / (4 * MGX_ALIGN_WAVES_PER_SIMD) - static_lds - 64u;
-    uint32_t lds_bytes = std::min<uint32_t>(fast_lds_bytes(l.Lmax), lds_budget) & ~15u;
-    const uint32_t w_slots = (uint32_t)std::min<uint64_t>(slots, wave_slots);
-    auto launch_groups = [&](int phase) -> int {
-        // tuning probe: MGX_EXT_GROUPS_PCT=50 launches half the resident groups (occupancy experiments)
-        const uint32_t pct = probe_env_pct("MGX_EXT_GROUPS_PCT");
-        const uint32_t groups = 8;
-        // three builds of the extension kernel (mgx_grp.hip): the product, the product with the CanonicalDBG branches (PRIMARY
-        // graphs), and the one with room for alternative paths (either kind of graph; MGX_PRIMARY_ALT_BUILD=1: A/B switch that
-        // sends PRIMARY graphs there as rounds 2-3 did)
-        const bool prim_to_alt = A->opt.primary_alt_build == 1;
-        const bool primary = A->dcfg.canonical >= 2;
-        const bool alt = agg_cap > 1 || (primary && prim_to_alt);
-        const bool prim = primary && !alt;
-        const uint32_t waves_cu = 4u * (uint32_t)(alt ? mgx_grp_waves_per_simd8_alt() : prim ? mgx_grp_waves_per_simd8_prim() : mgx_grp_waves_per_simd8());
-        const uint32_t static_lds = alt ? mgx_grp_static_lds8_alt() : prim ? mgx_grp_static_lds8_prim() : mgx_grp_static_lds8();
-        uint32_t per_wave = (160u * 1024u) / waves_cu - static_lds - 64u;
-        uint32_t per_group = std::min<uint32_t>(fast_lds_bytes(l.Lmax), per_wave / groups) & ~15u;
-        per_group = std::min<uint32_t>(per_group, probe_env_u32("MGX_EXT_LDS_CAP", per_group)) & ~15u;   // tuning probe
-        {
-            // Fewer reads than resident groups (long-read batches, single queries): spread them over the wavefronts.  The 8
-            // groups of a wavefront execute in lock-step, and reads of 1 .. 12 kbp side by side wait for each other's general
-            // steps two thirds of the time (config 0: 1.35 s with 8 reads per wavefront on 125 of 3072 wavefronts).  The arena
-            // slices stay what they are: slot = wavefront x groups_per_wave + group.
-            const uint64_t launch_groups_n = std::min<uint64_t>(slots, std::max<uint64_t>(1, slots * pct / 100));
-            const uint64_t resident_waves = (uint64_t)prop.multiProcessorCount * waves_cu;
-            const int gpw_env = A->opt.groups_per_wave;      // 0 = all 8
-            const uint64_t items = P.n_items ? P.n_items : n;                       // (a later pass of the multi-pass extension: its retry positions)
-            const uint64_t busy = std::min<uint64_t>(launch_groups_n, std::max<uint64_t>(1, items));
-            const uint64_t want_gpw = std::min<uint64_t>(groups, std::max<uint64_t>(1, (busy + resident_waves - 1) / resident_waves));
-            P.groups_per_wave = gpw_env >= 0 ? (uint32_t)std::min(8, gpw_env) : (want_gpw < groups ? (uint32_t)want_gpw : 0u);
+    if (A->opt.seed_wps == 8 && l.Lmax <= 192 && pl.slots >= (uint64_t)pl.cus * 4 * 8) {
+        // (measured on 150-bp reads: the kernel is 10 % faster with 4944 B of LDS per wavefront than with 5056 B, although
+        // both leave room for 32 wavefronts per CU; hence the wider margin)
+        uint32_t lds8 = lds_per_read(l.Lmax, 4 * MGX_SEED_WPS, static_lds, 192u);
+        lds8 = std::min<uint32_t>(lds8, probe_env_u32("MGX_SEED_LDS_CAP", lds8)) & ~15u;     // tuning probe
+        if (probe_env_set("MGX_SEED_LDS_PRINT")) fprintf(stderr, "k_seed: static_lds %u budget8 %u lds8 %u (fast_lds_bytes %u)\n", static_lds, lds_budget(4 * MGX_SEED_WPS, static_lds, 192u), lds8, fast_lds_bytes(l.Lmax));
+        if (primary) {
+            if (int rc = mgx_launch_seed_primary(&P, pl.cus * 4 * MGX_SEED_WPS, lds8, 1, A->hstream))
+                return fail(MGX_ERR_NO_DEVICE, "seeding kernel (PRIMARY): %d", rc);
+        } else {
+            // tuning probe: MGX_SEED_WAVES_PCT=50 launches half the resident wavefronts (is the kernel bound by what each
+            // wavefront waits for, or by what all of them move?)
+            const uint32_t spct = probe_env_pct("MGX_SEED_WAVES_PCT");
+            k_align<PH_SEED, MGX_SEED_WPS><<<std::max(1u, pl.cus * 4 * MGX_SEED_WPS * spct / 100), 64, lds8, A->hstream>>>(P, lds8);
         }
-        // One read per wavefront: the 64-lane instantiation (mgx_ext64.hip) — the read has the wavefront to itself, so it may as
-        // well use all of its lanes.  MGX_EXT64=0: A/B switch.
-        if (labeled) {
-            // label-aware extension: the labeled builds — 8 reads per wavefront (mgx_grp.hip, per-read program), or one read
-            // per wavefront on the 64-lane kernel (mgx_lab64.hip) for batches with fewer reads than resident wavefronts
-            const uint32_t wcu64 = 4u * (uint32_t)mgx_lab64_waves_per_simd();
-            const uint64_t resident64 = (uint64_t)prop.multiProcessorCount * wcu64;
-            const uint64_t items = P.n_items ? P.n_items : n;
-            if ((items <= resident64 && A->opt.ext64 != 0) || A->opt.ext64 == 2) {
-                const uint32_t lds64 = std::min<uint32_t>(fast_lds_bytes(l.Lmax), (160u * 1024u) / wcu64 - mgx_lab64_static_lds() - 128u) & ~15u;
-                P.groups_per_wave = 1;
-                A->kernels_ran |= MGX_KERNEL_LAB64;
-                return mgx_launch_lab64(&P, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(slots, resident64)), lds64, A->hstream);
-            }
-            const uint32_t wcu = 4u * (uint32_t)mgx_grp_waves_per_simd8_lab();
-            const uint32_t per_wave_l = (160u * 1024u) / wcu - mgx_grp_static_lds8_lab() - 64u;
-            const uint32_t per_group_l = std::min<uint32_t>(fast_lds_bytes(l.Lmax), per_wave_l / 8) & ~15u;
-            const int gpw_opt = A->opt.groups_per_wave;
-            P.groups_per_wave = gpw_opt > 0 ? (uint32_t)std::min(8, gpw_opt) : 0u;
-            A->kernels_ran |= MGX_KERNEL_GRP8_LAB;
-            return mgx_launch_align_grp8_lab(&P, (uint32_t)slots, per_group_l, phase, A->hstream);
-        }
-        const bool ext64 = A->opt.ext64 != 0;
-        if (ext64 && phase == PH_EXTEND && P.groups_per_wave == 1) {
-            const uint32_t wcu = 4u * (uint32_t)mgx_ext64_waves_per_simd();
-            const uint32_t lds64 = std::min<uint32_t>(fast_lds_bytes(l.Lmax), (160u * 1024u) / wcu - mgx_ext64_static_lds() - 128u) & ~15u;
-            A->kernels_ran |= MGX_KERNEL_EXT64;
-            ++g_kernel_launches[3];
-            return mgx_launch_ext64(&P, (uint32_t)std::min<uint64_t>(slots, std::max<uint64_t>(1, slots * pct / 100)), lds64, A->hstream);
-        }
-        A->kernels_ran |= alt ? MGX_KERNEL_GRP8_ALT : prim ? MGX_KERNEL_GRP8_PRIM : MGX_KERNEL_GRP8;
-        ++g_kernel_launches[alt ? 2 : prim ? 1 : 0];
-        return (alt ? mgx_launch_align_grp8_alt : prim ? mgx_launch_align_grp8_prim : mgx_launch_align_grp8)(&P, (uint32_t)std::min<uint64_t>(slots, std::max<uint64_t>(1, slots * pct / 100)), per_group, phase, A->hstream);      // never more groups than arena slices (a partial wavefront is fine: the kernel returns for slot >= n_groups)
-    };
-    A->split_ran = split;
-    A->kernels_ran = 0;
-    A->seedlane_launched = 0;
-    if (split) {
-        // The lane-per-read seeder (seed_lane.hpp, mgx_seedlane.hip) first: every lane seeds its own read and either publishes
-        // header, seeds and work key as the seeding kernel would, or lists the read for that kernel, which then seeds the
-        // list from scratch (no host round trip in between: the list's length stays on the device).
-        const bool seed_lane = A->opt.seed_lane != 0 && !probe_env_set("MGX_SEED_GROUPS") && A->packed_valid && P.pkw[0] && P.ivw[0]
-                               && (!A->dcfg.fwd_and_rc || (P.pkw[1] && P.ivw[1])) && P.mlen_fwd && P.rng_fwd
-                               && (!A->dcfg.fwd_and_rc || (P.mlen_rc && P.rng_rc))
-                               && seed_lane_enabled(A->dcfg, (uint32_t)A->graph->g.k, l.Lmax, true, true)
-                               && (A->opt.seed_lane == 1 || n >= 4096);
-        if (seed_lane && n) {
-            const bool long_reads = l.Lmax > (uint32_t)SL_SHORT_L;            // (the kernel's build with nine packed words per strand)
-            const uint32_t resident = (uint32_t)prop.multiProcessorCount * 4 * (uint32_t)mgx_seed_lane_waves_per_simd();
-            const uint32_t blocks1 = (uint32_t)std::min<uint64_t>(resident, (n + 63) / 64);
-            // (the second pass: what the first left — a sixth of a typical batch — with the big buffers)
-            const uint32_t blocks2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident / (long_reads ? 2 : 1), (n / 4 + 63) / 64));
-            const bool many = (uint64_t)A->graph->g.k >= A->dcfg.max_seed_length;
-            const uint32_t me1 = many ? (long_reads ? SL_SEEDS_1_MANY_LONG : SL_SEEDS_1_MANY) : SL_SEEDS_1, mp1 = many ? SL_PENDING_1_MANY : SL_PENDING_1;
-            const uint32_t me2 = long_reads ? SL_SEEDS_2_LONG : SL_SEEDS_2, mp2 = long_reads ? SL_PENDING_2_LONG : SL_PENDING_2;
-            const uint64_t words1 = seed_lane_wave_scratch_words(me1, mp1), words2 = seed_lane_wave_scratch_words(me2, mp2);
-            if (int rc = A->seedlane_scratch.ensure((size_t)std::max<uint64_t>(blocks1 * words1, blocks2 * words2) * 4)) return rc;
-            if (int rc = A->seedlane_params.ensure(2 * sizeof(SeedLaneParams))) return rc;
-            if (int rc = A->seedlane_bail.ensure(2 * (n * 4 + 4))) return rc;
-            if (int rc = A->seedlane_hist.ensure(32 * 8)) return rc;          // ([16 .. 24): section timers of -DMGX_SL_TIMERS builds)
-            HIP_TRY(hipMemsetAsync(A->seedlane_hist.p, 0, 32 * 8, A->hstream));
-            HIP_TRY(hipMemsetAsync(cur + 8, 0, 32, A->hstream));
-            const bool two = A->opt.seed_lane != 2;                          // (seed_lane=2: A/B switch, the first pass only)
-            SeedLaneParams SP[2];
-            memset(SP, 0, sizeof(SP));
-            uint32_t *list1 = A->seedlane_bail.as<uint32_t>(), *list2 = list1 + n + 1;
-            for (int ps = 0; ps < 2; ++ps) {
-                SP[ps].P = P;
-                SP[ps].P.n_items = n;
-                SP[ps].scratch = A->seedlane_scratch.as<uint32_t>();
-                SP[ps].max_entries = ps ? me2 : me1; SP[ps].max_pending = ps ? mp2 : mp1;
-                SP[ps].long_reads = long_reads ? 1u : 0u;
-                SP[ps].second_pass = (uint32_t)ps;
-                SP[ps].in_list = ps ? list1 : nullptr; SP[ps].in_count = ps ? cur + 8 : nullptr; SP[ps].in_count_back = ps ? cur + 11 : nullptr;
-                SP[ps].list_len = n;
-                SP[ps].bail_list = ps ? list2 : list1;
-                SP[ps].bail_count = ps ? cur + 10 : cur + 8;
-                SP[ps].bail_count_back = (!ps && two) ? cur + 11 : nullptr;
-                SP[ps].done_count = cur + 9;
-                // (why a read left: counted where it leaves for the wave program)
-                SP[ps].bail_hist = (ps || !two) ? A->seedlane_hist.as<unsigned long long>() : nullptr;
-            }
-            HIP_TRY(copy_sync(A, A->seedlane_params.p, SP, sizeof(SP), hipMemcpyHostToDevice));
-            if (int rc = mgx_launch_seed_lane(A->seedlane_params.p, blocks1, long_reads, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane-per-read seeder: %d", rc);
-            HIP_TRY(hipMemsetAsync(cur + 1, 0, 8, A->hstream));                      // rewind the read cursor
-            if (two) {
-                if (int rc = mgx_launch_seed_lane(A->seedlane_params.as<SeedLaneParams>() + 1, blocks2, long_reads, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane-per-read seeder, second pass: %d", rc);
-                HIP_TRY(hipMemsetAsync(cur + 1, 0, 8, A->hstream));
-            }
-            P.seed_list = two ? list2 : list1;
-            P.n_items_ptr = two ? cur + 10 : cur + 8;
-            A->seedlane_launched = 1;
-        }
-        HIP_TRY(hipEventRecord(A->ev[7], A->hstream));
-        if (probe_env_set("MGX_SEED_GROUPS")) {                 // A/B probe (needs a -DMGX_GRP_SEED_PROBE build of mgx_grp.hip)
-            if (int rc = launch_groups(PH_SEED)) return fail(MGX_ERR_NO_DEVICE, "group seeding kernel: %d", rc);
-        } else if (A->opt.seed_wps == 8 && l.Lmax <= 192 && slots >= (uint64_t)prop.multiProcessorCount * 4 * 8) {
-            // (measured on 150-bp reads: the kernel is 10 % faster with 4944 B of LDS per wavefront than with 5056 B, although
-            // both leave room for 32 wavefronts per CU; hence the wider margin)
-            const uint32_t budget8 = (160u * 1024u) / (4 * MGX_SEED_WPS) - static_lds - 192u;
-            uint32_t lds8 = std::min<uint32_t>(fast_lds_bytes(l.Lmax), budget8) & ~15u;
-            lds8 = std::min<uint32_t>(lds8, probe_env_u32("MGX_SEED_LDS_CAP", lds8)) & ~15u;     // tuning probe
-            if (probe_env_set("MGX_SEED_LDS_PRINT")) fprintf(stderr, "k_seed: static_lds %u budget8 %u lds8 %u (fast_lds_bytes %u)\n", static_lds, budget8, lds8, fast_lds_bytes(l.Lmax));
-            if (A->dcfg.canonical >= 2) {
-                if (int rc = mgx_launch_seed_primary(&P, (uint32_t)prop.multiProcessorCount * 4 * MGX_SEED_WPS, lds8, 1, A->hstream))
-                    return fail(MGX_ERR_NO_DEVICE, "seeding kernel (PRIMARY): %d", rc);
-            } else {
-                // tuning probe: MGX_SEED_WAVES_PCT=50 launches half the resident wavefronts (is the kernel bound by what each
-                // wavefront waits for, or by what all of them move?)
-                const uint32_t spct = probe_env_pct("MGX_SEED_WAVES_PCT");
-                k_align<PH_SEED, MGX_SEED_WPS><<<std::max(1u, (uint32_t)prop.multiProcessorCount * 4 * MGX_SEED_WPS * spct / 100), 64, lds8, A->hstream>>>(P, lds8);
-            }
-        } else if (A->dcfg.canonical >= 2) {
+    } else {
+        const uint32_t lds_bytes = lds_per_read(l.Lmax, 4 * MGX_ALIGN_WAVES_PER_SIMD, static_lds, 64u);
+        const uint32_t w_slots = (uint32_t)std::min<uint64_t>(pl.slots, pl.wave_slots);
+        if (primary) {
             if (int rc = mgx_launch_seed_primary(&P, w_slots, lds_bytes, 0, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "seeding kernel (PRIMARY): %d", rc);
         } else {
             k_align<PH_SEED><<<w_slots, 64, lds_bytes, A->hstream>>>(P, lds_bytes);
         }
-        HIP_TRY(hipGetLastError());
-        P.seed_list = nullptr; P.n_items_ptr = nullptr;
-        HIP_TRY(hipEventRecord(A->ev[4], A->hstream));
-        k_iota<<<(uint32_t)((n + 255) / 256), 256, 0, A->hstream>>>(A->order_in.as<uint32_t>(), n);
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(A->sort_tmp.p, sort_tmp_bytes, A->work_key.as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
-                                                   A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, work_key_bits(n), A->hstream));
-        HIP_TRY(hipMemsetAsync(cur + 1, 0, 8, A->hstream));                      // rewind the read cursor
-        P.order = A->order.as<uint32_t>();
-        HIP_TRY(hipEventRecord(A->ev[5], A->hstream));
-        // Passes.  MGX_MULTI_PASS=1 (default when a batch carries many seeds per read, see below): a pass extends at most
-        // one seed per read; reads with live seeds left write a resume record and are re-sorted by the work of their next
-        // seed for the next pass (AlignParams::resume_*).  Reads of a wavefront then differ by one extension at most,
-        // instead of waiting for the mate with the most seeds.  MGX_TWO_PASS=1: the older variant (pass 2 from scratch).
-        const int two_pass_env = A->opt.two_pass;
-        const int multi_env = A->opt.multi_pass;
-        bool multi = multi_env == 1 && !labeled && !A->cfg.post_chain_alignments;      // (resume records hold num_alternative_paths alignments)
-        if (multi_env < 0 && !labeled && !A->cfg.post_chain_alignments) {
-            // automatic: worth it when reads run many extensions, i.e. carry many seeds (sub-k seeds of a pan-genome: ~100 per
-            // read; a plain read: a handful).  The seeding kernel has finished counting them by now.
-            unsigned long long seeds_total = 0;
-            HIP_TRY(copy_sync(A, &seeds_total, cur + 2, 8, hipMemcpyDeviceToHost));
-            multi = n > 0 && seeds_total / n >= 24;
-        }
-        A->n_passes = 1;
-        A->lane_done = 0;
-        memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
-        HIP_TRY(hipEventRecord(A->ev[6], A->hstream));
-        bool nothing_left = false;
-        if (lane_ok && !multi && n) {
-            // every read through the lane kernel first, in the sorted order; what it lists goes on to the group kernel below
-            if (int rc = A->lane_bail.ensure(n * 4 + 4)) return rc;
-            if (int rc = A->lane_params.ensure(sizeof(LaneParams))) return rc;
-            if (int rc = A->lane_hist.ensure(64 * 8)) return rc;          // ([32 .. 63]: section timers of -DMGX_LANE_TIMERS builds)
-            HIP_TRY(hipMemsetAsync(A->lane_hist.p, 0, 64 * 8, A->hstream));
-            HIP_TRY(hipMemsetAsync(cur + 5, 0, 16, A->hstream));
-            LP.P = P;
-            LP.P.n_items = n;
-            LP.pk[0] = A->pk_fwd.as<uint64_t>(); LP.pk[1] = A->pk_rc.as<uint64_t>();
-            LP.iv[0] = A->iv_fwd.as<uint32_t>(); LP.iv[1] = A->iv_rc.as<uint32_t>();
-            LP.scratch = A->lane_scratch.as<uint8_t>();
-            LP.tag_seed = ++A->lane_epoch * 0x632BE5ABu;
-            LP.bail_list = A->lane_bail.as<uint32_t>();
-            LP.bail_count = cur + 5;
-            LP.done_count = cur + 6;
-            LP.bail_hist = A->lane_hist.as<unsigned long long>();
-            HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
-            uint32_t blocks = (uint32_t)std::min<uint64_t>(lane_blocks, (n + 63) / 64);
-            // (measurement only: MGX_LANE_BLOCKS_PCT < 100 launches that share of the resident wavefronts — is the kernel bound by
-            // the latency of its own dependent accesses, or by what the memory system serves per second?)
-            if (const char *pct = getenv("MGX_LANE_BLOCKS_PCT")) blocks = std::max<uint32_t>(1u, (uint32_t)((uint64_t)blocks * (uint64_t)atoi(pct) / 100));
-            if (int rc = lane_short ? mgx_launch_lane_short(A->lane_params.p, blocks, A->hstream) : mgx_launch_lane(A->lane_params.p, blocks, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel: %d", rc);
-            A->kernels_ran |= MGX_KERNEL_LANE;
-            ++g_kernel_launches[4];
-            HIP_TRY(hipEventRecord(A->ev[6], A->hstream));
-            unsigned long long counts[2] = { 0, 0 };
-            HIP_TRY(copy_sync(A, counts, cur + 5, 16, hipMemcpyDeviceToHost));     // (synchronises with the kernel)
-            A->lane_done = counts[1];
-            HIP_TRY(copy_sync(A, A->lane_hist_h, A->lane_hist.p, 32 * 8, hipMemcpyDeviceToHost));
-            if (getenv("MGX_LANE_TIMERS")) {
-                unsigned long long t[16];
-                HIP_TRY(copy_sync(A, t, A->lane_hist.as<unsigned long long>() + 32, sizeof(t), hipMemcpyDeviceToHost));
-                fprintf(stderr, "k_lane timers (cycles of lane 0, summed over %u wavefronts): setup %llu children %llu column %llu node-table %llu commit %llu frontier %llu trace %llu result %llu | emit %llu kernel %llu\n",
-                        blocks, t[0], t[1], t[2], t[7], t[3], t[4], t[5], t[6], t[8], t[9]);
-            }
-            HIP_TRY(hipMemsetAsync(cur + 1, 0, 8, A->hstream));                          // rewind the read cursor
-            P.order = A->lane_bail.as<uint32_t>();
-            P.n_items = counts[0];
-            nothing_left = counts[0] == 0;
-        }
-        if (nothing_left) {
-            // (every read finished in the lane kernel)
-        } else if (multi) {
-            const uint32_t rb = resume_rec_bytes(l, (uint32_t)std::max<uint64_t>(1, A->cfg.num_alternative_paths));
-            size_t fb = 0, tb = 0;
-            HIP_TRY(hipMemGetInfo(&fb, &tb));
-            fb += g_pool.held_bytes();
-            const uint64_t have = A->resume_pool[0].bytes + A->resume_pool[1].bytes;
-            uint64_t cap = std::min<uint64_t>(n, ((uint64_t)fb / 2 + have) / (2ull * rb));      // two pools
-            if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
-            if (cap == 0) multi = false;
-            if (multi) {
-                for (int b = 0; b < 2; ++b) {
-                    if (int rc = A->resume_pool[b].ensure(cap * rb, true)) return rc;
-                    if (int rc = A->retry_key[b].ensure(n * 4 + 4)) return rc;
-                }
-                if (int rc = A->retry_list2.ensure(n * 4 + 4)) return rc;
-                DevBuf *lists[2] = { &A->retry_list, &A->retry_list2 };
-                P.seed_limit = 1;
-                P.resume_rec_bytes = rb; P.resume_cap = (uint32_t)cap;
-                P.retry_count = cur + 3;
-                P.resume_in = nullptr; P.resume_reads = nullptr;
-                int out = 0;
-                uint64_t items = n;
-                for (uint32_t pass = 0;; ++pass) {
-                    P.resume_out = A->resume_pool[out].as<uint8_t>();
-                    P.retry_list = lists[out]->as<uint32_t>();
-                    P.retry_key = A->retry_key[out].as<uint32_t>();
-                    // later passes take more seeds per read, so that the number of launches stays small
-                    P.seed_limit = pass < 8 ? 1 : pass < 16 ? 4 : pass < 24 ? 16 : 0;
-                    HIP_TRY((hipError_t)launch_groups(PH_EXTEND));
-                    unsigned long long c = 0;
-                    HIP_TRY(copy_sync(A, &c, cur + 3, 8, hipMemcpyDeviceToHost));     // (synchronises with the pass)
-                    c = std::min<unsigned long long>(c, cap);
-                    A->n_passes = pass + 1;
-                    if (c == 0 || P.seed_limit == 0) break;
-                    // next pass: the retry positions of this one, sorted by their work key
-                    k_iota<<<(uint32_t)((c + 255) / 256), 256, 0, A->hstream>>>(A->order_in.as<uint32_t>(), c);
-                    size_t tmp_bytes = sort_tmp_bytes;
-                    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(A->sort_tmp.p, tmp_bytes, A->retry_key[out].as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
-                                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)c, 0, 12, A->hstream));
-                    HIP_TRY(hipMemsetAsync(cur + 1, 0, 8, A->hstream));              // rewind the read cursor
-                    HIP_TRY(hipMemsetAsync(cur + 3, 0, 8, A->hstream));              // and the retry counter
-                    P.order = A->order.as<uint32_t>();
-                    P.n_items = c;
-                    P.resume_in = A->resume_pool[out].as<uint8_t>();
-                    P.resume_reads = lists[out]->as<uint32_t>();
-                    items = c;
-                    out ^= 1;
-                }
-                (void)items;
-            }
-        }
-        if (!multi && !nothing_left) {
-            const bool two_pass = two_pass_env == 1 && !labeled;
-            for (int pass = 0; pass < (two_pass ? 2 : 1); ++pass) {
-                if (two_pass && pass == 0) {
-                    P.seed_limit = 1;
-                    P.retry_list = A->retry_list.as<uint32_t>();
-                    P.retry_count = cur + 3;
-                } else if (two_pass) {
-                    HIP_TRY(hipMemsetAsync(cur + 1, 0, 8, A->hstream));              // rewind the read cursor
-                    P.seed_limit = 0;
-                    P.order = A->retry_list.as<uint32_t>();
-                    P.n_items_ptr = cur + 3;
-                }
-                HIP_TRY((hipError_t)launch_groups(PH_EXTEND));
-            }
-        }
     }
-    HIP_TRY(hipEventRecord(A->ev[3], A->hstream));
+    HIP_TRY(hipGetLastError());
+    P.seed_list = nullptr; P.n_items_ptr = nullptr;
+    return MGX_OK;
+}
+
+// the reads in the order of their predicted extension work (the seeding kernels wrote the keys)
+static int sort_by_work(mgx_aligner *A, AlignPlan &pl) {
+    const uint64_t n = pl.n;
+    k_iota<<<(uint32_t)((n + 255) / 256), 256, 0, A->hstream>>>(A->order_in.as<uint32_t>(), n);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(A->sort_tmp.p, pl.sort_tmp_bytes, A->work_key.as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
+                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, work_key_bits(n), A->hstream));
+    HIP_TRY(clear_cursors(A, CUR_READ, CUR_READ));
+    pl.P.order = A->order.as<uint32_t>();
+    return MGX_OK;
+}
+
+// Multi-pass extension (option multi_pass; default: when a batch carries many seeds per read): a pass extends at most one seed
+// per read; reads with live seeds left write a resume record and are re-sorted by the work of their next seed for the next pass
+// (AlignParams::resume_*).  Reads of a wavefront then differ by one extension at most, instead of waiting for the mate with
+// the most seeds.
+static int choose_multi_pass(mgx_aligner *A, const AlignPlan &pl, bool *multi) {
+    *multi = false;
+    if (pl.labeled || A->cfg.post_chain_alignments) return MGX_OK;      // (resume records hold num_alternative_paths alignments)
+    *multi = A->opt.multi_pass == 1;
+    if (A->opt.multi_pass < 0) {
+        // automatic: worth it when reads run many extensions, i.e. carry many seeds (sub-k seeds of a pan-genome: ~100 per
+        // read; a plain read: a handful).  The seeding kernel has finished counting them by now.
+        unsigned long long seeds_total = 0;
+        HIP_TRY(copy_sync(A, &seeds_total, cursor(A, CUR_SEED), 8, hipMemcpyDeviceToHost));
+        *multi = pl.n > 0 && seeds_total / pl.n >= 24;
+    }
+    return MGX_OK;
+}
+
+// Every read through the lane-per-read kernel first, in the sorted order; what it lists goes on to the extension kernel
+// (the plan's order and item count become that list; *all_done: it is empty).
+static int extend_by_lanes(mgx_aligner *A, AlignPlan &pl, bool *all_done) {
+    AlignParams &P = pl.P;
+    LaneParams &LP = pl.LP;
+    const uint64_t n = pl.n;
+    if (int rc = A->lane_bail.ensure(n * 4 + 4)) return rc;
+    if (int rc = A->lane_params.ensure(sizeof(LaneParams))) return rc;
+    if (int rc = A->lane_hist.ensure(64 * 8)) return rc;          // ([32 .. 63]: section timers of -DMGX_LANE_TIMERS builds)
+    HIP_TRY(hipMemsetAsync(A->lane_hist.p, 0, 64 * 8, A->hstream));
+    HIP_TRY(clear_cursors(A, CUR_LANE_BAIL, CUR_LANE_DONE));
+    LP.P = P;
+    LP.P.n_items = n;
+    LP.pk[0] = A->pk_fwd.as<uint64_t>(); LP.pk[1] = A->pk_rc.as<uint64_t>();
+    LP.iv[0] = A->iv_fwd.as<uint32_t>(); LP.iv[1] = A->iv_rc.as<uint32_t>();
+    LP.scratch = A->lane_scratch.as<uint8_t>();
+    LP.tag_seed = ++A->lane_epoch * 0x632BE5ABu;
+    LP.bail_list = A->lane_bail.as<uint32_t>();
+    LP.bail_count = cursor(A, CUR_LANE_BAIL);
+    LP.done_count = cursor(A, CUR_LANE_DONE);
+    LP.bail_hist = A->lane_hist.as<unsigned long long>();
+    HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
+    uint32_t blocks = (uint32_t)std::min<uint64_t>(pl.lane_blocks, (n + 63) / 64);
+    if (int pct; env_int("MGX_LANE_BLOCKS_PCT", &pct)) blocks = std::max<uint32_t>(1u, (uint32_t)((uint64_t)blocks * (uint64_t)pct / 100));
+    if (int rc = mgx_launch_lane(A->lane_params.p, blocks, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel: %d", rc);
+    A->kernels_ran |= MGX_KERNEL_LANE;
+    ++g_kernel_launches[CNT_LANE];
+    HIP_TRY(hipEventRecord(A->ev[EV_LANE_END], A->hstream));
+    unsigned long long counts[2] = { 0, 0 };      // CUR_LANE_BAIL, CUR_LANE_DONE
+    HIP_TRY(copy_sync(A, counts, cursor(A, CUR_LANE_BAIL), 16, hipMemcpyDeviceToHost));     // (synchronises with the kernel)
+    A->lane_done = counts[1];
+    HIP_TRY(copy_sync(A, A->lane_hist_h, A->lane_hist.p, 32 * 8, hipMemcpyDeviceToHost));
+    if (int on; env_int("MGX_LANE_TIMERS", &on)) {
+        unsigned long long t[16];
+        HIP_TRY(copy_sync(A, t, A->lane_hist.as<unsigned long long>() + 32, sizeof(t), hipMemcpyDeviceToHost));
+        fprintf(stderr, "k_lane timers (cycles of lane 0, summed over %u wavefronts): setup %llu children %llu column %llu node-table %llu commit %llu frontier %llu trace %llu result %llu | emit %llu kernel %llu\n",
+                blocks, t[0], t[1], t[2], t[7], t[3], t[4], t[5], t[6], t[8], t[9]);
+    }
+    HIP_TRY(clear_cursors(A, CUR_READ, CUR_READ));
+    P.order = A->lane_bail.as<uint32_t>();
+    P.n_items = counts[0];
+    *all_done = counts[0] == 0;
+    return MGX_OK;
+}
+
+// One launch of the extension kernel on the plan's work items (P.order / P.n_items): which build, on how many groups or
+// wavefronts (never more than arena slices), with how much LDS per read.  Returns the launcher's hipError_t.
+static int launch_extension(mgx_aligner *A, AlignPlan &pl) {
+    const uint32_t Lmax = A->lim.Lmax;
+    const int gpw_opt = A->opt.groups_per_wave;                             // -1 = automatic, 0 = all 8
+    const uint64_t items = pl.P.n_items ? pl.P.n_items : pl.n;             // (a later pass of the multi-pass extension: its retry positions)
+    const ExtBuild *b = pl.grp;
+    uint32_t gpw, count, lds;         // AlignParams::groups_per_wave (0 = all 8); groups (8-lane builds) or wavefronts; LDS per read
+    if (pl.labeled) {
+        // label-aware extension: the labeled builds — 8 reads per wavefront (mgx_grp.hip, per-read program), or one read
+        // per wavefront on the 64-lane kernel (mgx_lab64.hip) for batches with fewer reads than resident wavefronts
+        const ExtBuild &lab64 = g_ext_builds[EXT_LAB64];
+        const uint64_t resident64 = (uint64_t)pl.cus * waves_per_cu(lab64);
+        if ((items <= resident64 && A->opt.ext64 != 0) || A->opt.ext64 == 2) {
+            b = &lab64; gpw = 1;
+            count = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(pl.slots, resident64));
+        } else {
+            gpw = gpw_opt > 0 ? (uint32_t)std::min(8, gpw_opt) : 0u;
+            count = (uint32_t)pl.slots;
+        }
+    } else {
+        // tuning probe: MGX_EXT_GROUPS_PCT=50 launches half the resident groups (occupancy experiments)
+        const uint32_t pct = probe_env_pct("MGX_EXT_GROUPS_PCT");
+        count = (uint32_t)std::min<uint64_t>(pl.slots, std::max<uint64_t>(1, pl.slots * pct / 100));
+        // Fewer reads than resident groups (long-read batches, single queries): spread them over the wavefronts.  The 8
+        // groups of a wavefront execute in lock-step, and reads of 1 .. 12 kbp side by side wait for each other's general
+        // steps two thirds of the time (config 0: 1.35 s with 8 reads per wavefront on 125 of 3072 wavefronts).  The arena
+        // slices stay what they are: slot = wavefront x groups_per_wave + group.
+        const uint64_t resident_waves = (uint64_t)pl.cus * waves_per_cu(*pl.grp);
+        const uint64_t busy = std::min<uint64_t>(count, std::max<uint64_t>(1, items));
+        const uint64_t want_gpw = std::min<uint64_t>(8, std::max<uint64_t>(1, (busy + resident_waves - 1) / resident_waves));
+        gpw = gpw_opt >= 0 ? (uint32_t)std::min(8, gpw_opt) : (want_gpw < 8 ? (uint32_t)want_gpw : 0u);
+        // One read per wavefront: the 64-lane instantiation (mgx_ext64.hip) — the read has the wavefront to itself, so it may as
+        // well use all of its lanes.  (Option ext64=0: the 8-lane groups all the same.)
+        if (A->opt.ext64 != 0 && gpw == 1) b = &g_ext_builds[EXT_EXT64];
+    }
+    if (b->launch_64) {
+        lds = lds_per_read(Lmax, waves_per_cu(*b), b->static_lds(), 128u);
+    } else {
+        lds = lds_per_read(Lmax, waves_per_cu(*b), b->static_lds(), 64u, 8);
+        if (!pl.labeled) lds = std::min<uint32_t>(lds, probe_env_u32("MGX_EXT_LDS_CAP", lds)) & ~15u;   // tuning probe
+    }
+    pl.P.groups_per_wave = gpw;
+    A->kernels_ran |= b->kernel_bit;
+    if (b->counter != CNT_NONE) ++g_kernel_launches[b->counter];
+    // (8-lane builds: a partial last wavefront is fine, the kernel returns for slot >= n_groups)
+    return b->launch_64 ? b->launch_64(&pl.P, count, lds, A->hstream) : b->launch_grp(&pl.P, count, lds, PH_EXTEND, A->hstream);
+}
+
+// The passes of the multi-pass extension (choose_multi_pass): launch, count the reads that want another pass, sort their
+// retry positions by the work of their next seed, again.
+static int extend_multi_pass(mgx_aligner *A, AlignPlan &pl) {
+    AlignParams &P = pl.P;
+    const uint64_t n = pl.n;
+    const uint32_t rb = resume_rec_bytes(A->lim, (uint32_t)std::max<uint64_t>(1, A->cfg.num_alternative_paths));
+    size_t fb = 0, tb = 0;
+    HIP_TRY(hipMemGetInfo(&fb, &tb));
+    fb += g_pool.held_bytes();
+    const uint64_t have = A->resume_pool[0].bytes + A->resume_pool[1].bytes;
+    uint64_t cap = std::min<uint64_t>(n, ((uint64_t)fb / 2 + have) / (2ull * rb));      // two pools
+    if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
+    if (cap == 0) {               // (no room for resume records: every seed of a read in one launch)
+        HIP_TRY((hipError_t)launch_extension(A, pl));
+        return MGX_OK;
+    }
+    for (int b = 0; b < 2; ++b) {
+        if (int rc = A->resume_pool[b].ensure(cap * rb, true)) return rc;
+        if (int rc = A->retry_key[b].ensure(n * 4 + 4)) return rc;
+    }
+    if (int rc = A->retry_list2.ensure(n * 4 + 4)) return rc;
+    DevBuf *lists[2] = { &A->retry_list, &A->retry_list2 };
+    P.resume_rec_bytes = rb; P.resume_cap = (uint32_t)cap;
+    P.retry_count = cursor(A, CUR_RETRY);
+    P.resume_in = nullptr; P.resume_reads = nullptr;
+    int out = 0;
+    for (uint32_t pass = 0;; ++pass) {
+        P.resume_out = A->resume_pool[out].as<uint8_t>();
+        P.retry_list = lists[out]->as<uint32_t>();
+        P.retry_key = A->retry_key[out].as<uint32_t>();
+        // later passes take more seeds per read, so that the number of launches stays small
+        P.seed_limit = pass < 8 ? 1 : pass < 16 ? 4 : pass < 24 ? 16 : 0;
+        HIP_TRY((hipError_t)launch_extension(A, pl));
+        unsigned long long c = 0;
+        HIP_TRY(copy_sync(A, &c, cursor(A, CUR_RETRY), 8, hipMemcpyDeviceToHost));     // (synchronises with the pass)
+        c = std::min<unsigned long long>(c, cap);
+        A->n_passes = pass + 1;
+        if (c == 0 || P.seed_limit == 0) break;
+        // next pass: the retry positions of this one, sorted by their work key
+        k_iota<<<(uint32_t)((c + 255) / 256), 256, 0, A->hstream>>>(A->order_in.as<uint32_t>(), c);
+        size_t tmp_bytes = pl.sort_tmp_bytes;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(A->sort_tmp.p, tmp_bytes, A->retry_key[out].as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
+                                                   A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)c, 0, 12, A->hstream));
+        HIP_TRY(clear_cursors(A, CUR_READ, CUR_READ));
+        HIP_TRY(clear_cursors(A, CUR_RETRY, CUR_RETRY));
+        P.order = A->order.as<uint32_t>();
+        P.n_items = c;
+        P.resume_in = A->resume_pool[out].as<uint8_t>();
+        P.resume_reads = lists[out]->as<uint32_t>();
+        out ^= 1;
+    }
+    return MGX_OK;
+}
+
+static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax) {
+    {
+        std::string err;
+        int rc = derive_limits(A->cfg, A->have_user_lim ? &A->user_lim : nullptr, Lmax, &A->lim, &err, A->anno != nullptr, A->label_scale);
+        if (rc) return fail(rc, "%s", err.c_str());
+    }
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, A->graph->device));
+    AlignPlan pl;
+    pl.n = n;
+    pl.labeled = A->anno != nullptr;
+    pl.cus = (uint32_t)prop.multiProcessorCount;
+    if (int rc = plan_lane(A, pl)) return rc;
+    if (int rc = size_arena(A, pl)) return rc;
+    if (int rc = size_buffers(A, pl)) return rc;
+    fill_params(A, pl, d_seqs, d_offsets);
+    HIP_TRY(hipEventRecord(A->ev[EV_ALIGN_BEGIN], A->hstream));
+    A->kernels_ran = 0;
+    A->seedlane_launched = 0;
+    if (int rc = seed_by_lanes(A, pl)) return rc;
+    HIP_TRY(hipEventRecord(A->ev[EV_SEED_LANE_END], A->hstream));
+    if (int rc = seed_by_waves(A, pl)) return rc;
+    HIP_TRY(hipEventRecord(A->ev[EV_SEEDED], A->hstream));
+    if (int rc = sort_by_work(A, pl)) return rc;
+    HIP_TRY(hipEventRecord(A->ev[EV_SORTED], A->hstream));
+    bool multi = false;
+    if (int rc = choose_multi_pass(A, pl, &multi)) return rc;
+    A->n_passes = 1;
+    A->lane_done = 0;
+    memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
+    HIP_TRY(hipEventRecord(A->ev[EV_LANE_END], A->hstream));      // (recorded again behind the lane kernel, if it runs)
+    bool all_done = false;        // every read finished in the lane kernel
+    if (pl.lane_ok && !multi && n) {
+        if (int rc = extend_by_lanes(A, pl, &all_done)) return rc;
+    }
+    if (multi) {
+        if (int rc = extend_multi_pass(A, pl)) return rc;
+    } else if (!all_done) {
+        HIP_TRY((hipError_t)launch_extension(A, pl));
+    }
+    HIP_TRY(hipEventRecord(A->ev[EV_ALIGN_END], A->hstream));
     return MGX_OK;
 }
 
@@ -1591,7 +1656,7 @@ static int collect_stats(mgx_aligner *A, bool mapped, bool aligned) {
     s.n_lane_reads = A->lane_done;
     s.n_lane_lines = ks.lane_lines; s.n_lane_columns = ks.lane_columns;
     for (int x = 0; x < 32; ++x) s.lane_bail_reads[x] = A->lane_hist_h[x];
-    if (aligned && A->seedlane_launched && getenv("MGX_SL_TIMERS")) {
+    if (int on; aligned && A->seedlane_launched && env_int("MGX_SL_TIMERS", &on)) {
         unsigned long long t[8];
         HIP_TRY(copy_sync(A, t, A->seedlane_hist.as<unsigned long long>() + 16, sizeof(t), hipMemcpyDeviceToHost));
         fprintf(stderr, "k_seed_lane timers (cycles of lane 0, summed over the wavefronts): strands %llu masks %llu scan %llu walks %llu dust %llu ranges+enumerate %llu publish %llu wave-mates %llu\n",
@@ -1599,21 +1664,21 @@ static int collect_stats(mgx_aligner *A, bool mapped, bool aligned) {
     }
     if (aligned && A->seedlane_launched) {
         unsigned long long done = 0, why[16];
-        HIP_TRY(copy_sync(A, &done, A->cursors.as<unsigned long long>() + 9, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(A, &done, cursor(A, CUR_SL_DONE), 8, hipMemcpyDeviceToHost));
         HIP_TRY(copy_sync(A, why, A->seedlane_hist.p, sizeof(why), hipMemcpyDeviceToHost));
         s.n_seed_lane_reads = done;
         for (int x = 0; x < 16; ++x) s.seed_lane_left_reads[x] = why[x];
     }
     for (int x = 0; x < 8; ++x) { s.phase_cycles[x] = ks.cyc[x]; s.extend_cycles[x] = ks.xcyc[x]; }
     float ms = 0;
-    if (mapped) { HIP_TRY(hipEventElapsedTime(&ms, A->ev[0], A->ev[1])); s.seed_kernel_ms = ms; }
-    if (aligned) { HIP_TRY(hipEventElapsedTime(&ms, A->ev[2], A->ev[3])); s.align_kernel_ms = ms; }
-    if (aligned && A->split_ran) {
-        HIP_TRY(hipEventElapsedTime(&ms, A->ev[2], A->ev[4])); s.seeding_ms = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, A->ev[4], A->ev[5])); s.sort_ms = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, A->ev[5], A->ev[3])); s.extend_ms = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, A->ev[5], A->ev[6])); s.lane_ms = ms;
-        if (A->seedlane_launched) { HIP_TRY(hipEventElapsedTime(&ms, A->ev[2], A->ev[7])); s.seed_lane_ms = ms; }
+    if (mapped) { HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_MAP_BEGIN], A->ev[EV_MAP_END])); s.seed_kernel_ms = ms; }
+    if (aligned) {
+        HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_ALIGN_BEGIN], A->ev[EV_ALIGN_END])); s.align_kernel_ms = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_ALIGN_BEGIN], A->ev[EV_SEEDED])); s.seeding_ms = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_SEEDED], A->ev[EV_SORTED])); s.sort_ms = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_SORTED], A->ev[EV_ALIGN_END])); s.extend_ms = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_SORTED], A->ev[EV_LANE_END])); s.lane_ms = ms;
+        if (A->seedlane_launched) { HIP_TRY(hipEventElapsedTime(&ms, A->ev[EV_ALIGN_BEGIN], A->ev[EV_SEED_LANE_END])); s.seed_lane_ms = ms; }
     }
     return MGX_OK;
 }
@@ -1673,35 +1738,35 @@ void *mgx_aligner_get_stream(const mgx_aligner *A) { return A ? (void *)A->hstre
 
 int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
     if (!A) return fail(MGX_ERR_INVALID, "null argument");
-    AlignMode m = parse_mode(name);
+    if (!name) return fail(MGX_ERR_INVALID, "unknown pipeline '(null)'");
     // "+general" / "+chain" suffix-free test switches: the extension's register-resident chain path off / on
-    if (name && !strcmp(name, "general")) { A->no_fast = true; return MGX_OK; }
-    if (name && !strcmp(name, "chain")) { A->no_fast = false; return MGX_OK; }
-    if (name && strchr(name, '=')) {
+    if (!strcmp(name, "general")) { A->no_fast = true; return MGX_OK; }
+    if (!strcmp(name, "chain")) { A->no_fast = false; return MGX_OK; }
+    if (strchr(name, '=')) {
         const std::string key(name, strchr(name, '=') - name);
         const int v = atoi(strchr(name, '=') + 1);
         mgx_aligner::Options &o = A->opt;
         if (key == "ext64") o.ext64 = v;
         else if (key == "groups_per_wave") o.groups_per_wave = std::min(8, v);
         else if (key == "multi_pass") o.multi_pass = v;
-        else if (key == "two_pass") o.two_pass = v;
         else if (key == "no_compact") o.no_compact = v;
         else if (key == "no_alias") o.no_alias = v;
         else if (key == "no_bt_runs") o.no_bt_runs = v;
         else if (key == "no_flat") o.no_flat = v;
-        else if (key == "primary_alt_build") o.primary_alt_build = v;
         else if (key == "lane") o.lane = v;
-        else if (key == "lane_short") o.lane_short = v;
         else if (key == "device_share") o.device_share = std::max(1, std::min(v, 64));
         else if (key == "map_pipe") o.map_pipe = v;
         else if (key == "seed_wps") o.seed_wps = v;
-        else if (key == "seed_lane") o.seed_lane = v;
+        else if (key == "seed_lane") {
+            if (v < -1 || v > 1) return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
+            o.seed_lane = v;
+        }
         else if (key == "retry_capacity") A->retry_capacity = v != 0;
         else return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
         return MGX_OK;
     }
-    if (m == MODE_BAD) return fail(MGX_ERR_INVALID, "unknown pipeline '%s'", name ? name : "(null)");
-    A->mode = m;
+    // (the one pipeline there is, see the top of this file: its name selects nothing)
+    if (strcmp(name, "split8")) return fail(MGX_ERR_INVALID, "unknown pipeline '%s'", name);
     return MGX_OK;
 }
 
@@ -1734,15 +1799,13 @@ int mgx_align_batch_device(mgx_aligner *A, const char *seqs, const uint64_t *off
         // both streams keep counting past their capacity: reads that found no room got a capacity status and the
         // stage is redone with what it asked for
         unsigned long long out_wanted = 0, seeds_wanted = 0;
-        HIP_TRY(copy_sync(A, &out_wanted, A->cursors.as<unsigned long long>(), 8, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(A, &out_wanted, cursor(A, CUR_OUT), 8, hipMemcpyDeviceToHost));
         bool again = false;
         if (out_wanted > A->out_words) { A->out_min_words = out_wanted + out_wanted / 8 + 1024; again = true; }
-        if (A->split_ran) {
-            HIP_TRY(copy_sync(A, &seeds_wanted, A->cursors.as<unsigned long long>() + 2, 8, hipMemcpyDeviceToHost));
-            if (seeds_wanted > A->seed_cap) {
-                A->seed_scale = seeds_wanted / std::max<uint64_t>(1, A->seed_cap / A->seed_scale) + 2;
-                again = true;
-            }
+        HIP_TRY(copy_sync(A, &seeds_wanted, cursor(A, CUR_SEED), 8, hipMemcpyDeviceToHost));
+        if (seeds_wanted > A->seed_cap) {
+            A->seed_scale = seeds_wanted / std::max<uint64_t>(1, A->seed_cap / A->seed_scale) + 2;
+            again = true;
         }
         if (!again) break;
     }
@@ -1760,7 +1823,7 @@ int mgx_fetch_results(mgx_aligner *A, mgx_results *out) {
     unsigned long long used = 0;
     if (n) {
         HIP_TRY(copy_sync(A, A->h_results.data(), A->results.p, n * sizeof(ReadResult), hipMemcpyDeviceToHost));
-        HIP_TRY(copy_sync(A, &used, A->cursors.p, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(A, &used, cursor(A, CUR_OUT), 8, hipMemcpyDeviceToHost));
         used = std::min<unsigned long long>(used, A->out_words);
     }
     A->h_stream.resize(used);
@@ -1800,7 +1863,7 @@ int mgx_device_results(mgx_aligner *A, const void **headers, uint64_t *header_by
                        const void **stream, uint64_t *stream_words) {
     if (!A) return fail(MGX_ERR_INVALID, "null argument");
     unsigned long long used = 0;
-    if (A->n_reads) HIP_TRY(copy_sync(A, &used, A->cursors.p, 8, hipMemcpyDeviceToHost));
+    if (A->n_reads) HIP_TRY(copy_sync(A, &used, cursor(A, CUR_OUT), 8, hipMemcpyDeviceToHost));
     used = std::min<unsigned long long>(used, A->out_words);
     *headers = A->results.p; *header_bytes = sizeof(ReadResult); *n_queries = A->n_reads;
     *stream = A->stream.p; *stream_words = used;
@@ -1885,7 +1948,7 @@ static int retry_capacity_queries(mgx_aligner *A, const char *d_seqs, const uint
         // (an attempt that fails — out of memory at the inflated limits, say — ends the retry: what the batch and the earlier
         // attempts produced stays valid and is what the caller gets, statuses included)
         if (aligner_create(A->graph, &A->cfg, &lim, A->anno, &tmp) != MGX_OK) break;
-        tmp->opt = A->opt; tmp->mode = A->mode; tmp->no_fast = A->no_fast;
+        tmp->opt = A->opt; tmp->no_fast = A->no_fast;
         tmp->hstream = A->hstream;                        // (borrowed: the retry runs where the batch ran)
         tmp->retry_capacity = false;
         tmp->label_scale = 2u << attempt;

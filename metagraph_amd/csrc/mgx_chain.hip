@@ -23,9 +23,7 @@
 #include <vector>
 
 #include "../../include/mgx.h"
-
-extern "C" int mgx_device_count(void);
-extern "C" void mgx_set_last_error(const char *msg);
+#include "kernel_units.hpp"
 
 namespace {
 

@@ -7,8 +7,7 @@
 
 #include "../../include/mgx.h"
 #include "boss_files.hpp"
-
-extern "C" void mgx_set_last_error(const char *msg);     // mgx.hip
+#include "kernel_units.hpp"
 
 struct mgx_column_file {
     mgx::files::ColumnFile f;

@@ -30,8 +30,7 @@
 #include <vector>
 
 #include "../../include/mgx.h"
-
-extern "C" void mgx_set_last_error(const char *msg);     // mgx.hip
+#include "kernel_units.hpp"
 
 namespace {
 

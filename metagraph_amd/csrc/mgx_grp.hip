@@ -31,6 +31,7 @@
 #define MGX_PARAMS_IN_LDS 1     // the kernel keeps one copy of AlignParams in LDS; the per-read program reads it with ds_ loads
 #include "wave_group.hpp"
 #include "align_core.hpp"
+#include "kernel_units.hpp"
 
 using namespace mgx;
 
@@ -110,7 +111,7 @@ __global__ void __launch_bounds__(64, MGX_GRP_WAVES_PER_SIMD) MGX_SUFFIX(MGX_CAT
             else flat_bt_all(w);
         }
     }
-#if defined(MGX_ALT_BUILD) || defined(MGX_KEEP_LEGACY) || defined(MGX_GRP_SEED_PROBE)
+#if defined(MGX_ALT_BUILD) || defined(MGX_KEEP_LEGACY)
     else {
         for (;;) {
             uint64_t read = 0;
@@ -138,18 +139,13 @@ __global__ void __launch_bounds__(64, MGX_GRP_WAVES_PER_SIMD) MGX_SUFFIX(MGX_CAT
 }
 
 // n_groups = arena slices; lds_bytes = dynamic LDS per group
-// phase = PH_BOTH (fused) or PH_EXTEND (after the seeding kernel)
+// phase = PH_EXTEND (after the seeding kernels): the only half of the wave program that is instantiated for sub-wave groups
 extern "C" int MGX_SUFFIX(MGX_CAT(mgx_launch_align_grp, MGX_GROUP))(const void *params, uint32_t n_groups, uint32_t lds_bytes, int phase, void *stream) {
+    static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES, "AlignParams differs from what mgx.hip passes");
     const AlignParams &P = *static_cast<const AlignParams *>(params);
     const uint32_t gpw = P.groups_per_wave ? P.groups_per_wave : (uint32_t)GROUPS_PER_WAVEFRONT;
     uint32_t blocks = (n_groups + gpw - 1) / gpw;
-#if defined(MGX_GRP_SEED_PROBE) && !defined(MGX_ALT_BUILD)
-    if (phase == PH_SEED) {          // A/B probe: the seeding half with 8 lanes per read
-        MGX_SUFFIX(MGX_CAT(k_align_grp, MGX_GROUP))<PH_SEED><<<blocks, 64, lds_bytes * GROUPS_PER_WAVEFRONT, (hipStream_t)stream>>>(P, lds_bytes, n_groups);
-        return (int)hipGetLastError();
-    }
-#endif
-    if (phase != PH_EXTEND) return (int)hipErrorInvalidValue;      // only the extension half is instantiated for sub-wave groups
+    if (phase != PH_EXTEND) return (int)hipErrorInvalidValue;
     MGX_SUFFIX(MGX_CAT(k_align_grp, MGX_GROUP))<PH_EXTEND><<<blocks, 64, lds_bytes * GROUPS_PER_WAVEFRONT, (hipStream_t)stream>>>(P, lds_bytes, n_groups);
     return (int)hipGetLastError();
 }

@@ -13,10 +13,12 @@
 #define MGX_ALIGN_WAVES_PER_SIMD 2
 #include "wave.hpp"
 #include "seed_kernel.hpp"
+#include "kernel_units.hpp"
 
 using namespace mgx;
 
 extern "C" int mgx_launch_lab64(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream) {
+    static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES, "AlignParams differs from what mgx.hip passes");
     const AlignParams &P = *static_cast<const AlignParams *>(params);
     k_align<PH_EXTEND><<<blocks, 64, lds_bytes, (hipStream_t)stream>>>(P, lds_bytes);
     return (int)hipGetLastError();

@@ -11,25 +11,11 @@
 // full-line stores); the node table in a private slice per lane.
 #include <hip/hip_runtime.h>
 
-// Built twice: as is — reads of up to 256 characters, two wavefronts per SIMD — and with -DMGX_LANE_SHORT for batches whose
-// longest read has at most 160 characters (the benchmark's 150-bp reads): seven packed words per strand instead of ten, which
-// together with the CIGAR runs and six cold words that left the LDS in round 6 fits THREE wavefronts per SIMD into the LDS
-// (52 rows x 256 B = 13 312 B per wavefront); the register budget of three (168) is the compiler's to meet.
-#ifdef MGX_LANE_SHORT
-#define mgx mgx_lane_short_ns
-#define MGX_LANE_MAX_L 160
-#ifndef MGX_LANE_WAVES_PER_SIMD
-#define MGX_LANE_WAVES_PER_SIMD 3
-#endif
-#define k_lane k_lane_short
-#define mgx_launch_lane mgx_launch_lane_short
-#define mgx_lane_waves_per_simd mgx_lane_short_waves_per_simd
-#else
 #define mgx mgx_lane_ns
-#endif
 #include "wave.hpp"
 #include "graph_build.hpp"
 #include "lane_read.hpp"
+#include "kernel_units.hpp"
 
 using namespace mgx;
 
@@ -167,6 +153,7 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
 // blocks = resident wavefronts (wavefront b owns LaneParams::scratch + b * wave_stride)
 // d_params: the LaneParams of this launch in device memory
 extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream) {
+    static_assert(sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES, "LaneParams differs from what mgx.hip passes");
     k_lane<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     return (int)hipGetLastError();
 }

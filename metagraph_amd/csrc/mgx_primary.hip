@@ -9,10 +9,12 @@
 #define MGX_NO_EXTEND 1
 #include "wave.hpp"
 #include "seed_kernel.hpp"
+#include "kernel_units.hpp"
 
 using namespace mgx;
 
 extern "C" int mgx_launch_seed_primary(const void *params, uint32_t blocks, uint32_t lds_bytes, int wps8, void *stream) {
+    static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES, "AlignParams differs from what mgx.hip passes");
     const AlignParams &P = *static_cast<const AlignParams *>(params);
     if (wps8) k_align<PH_SEED, MGX_SEED_WPS><<<blocks, 64, lds_bytes, (hipStream_t)stream>>>(P, lds_bytes);
     else k_align<PH_SEED><<<blocks, 64, lds_bytes, (hipStream_t)stream>>>(P, lds_bytes);

@@ -13,6 +13,7 @@
 #include "wave.hpp"
 #include "graph_build.hpp"
 #include "seed_lane.hpp"
+#include "kernel_units.hpp"
 
 using namespace mgx;
 
@@ -115,6 +116,7 @@ __global__ void __launch_bounds__(64, MGX_SEEDLANE_WAVES_PER_SIMD) k_seed_lane(c
 // blocks = resident wavefronts (wavefront b owns SeedLaneParams::scratch + b * seed_lane_wave_scratch_words(...))
 // long_reads: the build for reads of more than SL_SHORT_L characters (SeedLaneParams::long_reads says the same to the host side)
 extern "C" int mgx_launch_seed_lane(const void *d_params, uint32_t blocks, int long_reads, void *stream) {
+    static_assert(sizeof(SeedLaneParams) == MGX_SEED_LANE_PARAMS_BYTES, "SeedLaneParams differs from what mgx.hip passes");
     if (long_reads) k_seed_lane<SL_QWORDS_LONG><<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const SeedLaneParams *>(d_params));
     else k_seed_lane<SL_QWORDS_SHORT><<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const SeedLaneParams *>(d_params));
     return (int)hipGetLastError();

@@ -197,9 +197,12 @@ def test_reads_with_invalid_and_lower_case_characters_on_gpu(k, kernels):
 def test_unknown_pipeline_is_an_error():
     g, _ = make_world(3, 9, genome_len=300, n_reads=0)
     A = aligner.Aligner(gpu_graph(g), capi.config_cli(9))
-    with pytest.raises(aligner.MgxError) as e:
-        A.set_pipeline("warp32")
-    assert e.value.code == capi.MGX_ERR_INVALID
+    # (options whose A/B experiment is over are gone and answered like any unknown key)
+    for name in ("warp32", "two_pass=1", "primary_alt_build=1", "lane_short=1"):
+        with pytest.raises(aligner.MgxError) as e:
+            A.set_pipeline(name)
+        assert e.value.code == capi.MGX_ERR_INVALID, name
+    A.set_pipeline("split8")          # the name of the one pipeline is accepted
 
 
 def test_align_forward_only_and_no_min_exact_match(kernels):
