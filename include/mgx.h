@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* 6 (round 6, late): mgx_gather_* (RCCL gather of the device results); 5 (round 6): mgx_stats::n_seed_lane_reads / seed_lane_ms / seed_lane_left_reads, streams, coordinates,
+#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_map_summary_batch / mgx_map_present / mgx_format_map / mgx_map_kernel_launch_counts
+                                * (`align --map`: per-read k-mer counts, presence, --align-length < k);
+                                * 6 (round 6, late): mgx_gather_* (RCCL gather of the device results); 5 (round 6): mgx_stats::n_seed_lane_reads / seed_lane_ms / seed_lane_left_reads, streams, coordinates,
                                 * mgx_chain_seeds; 4 (round 5): mgx_stats::n_capacity_retried, mgx_chain_alignments, post_chain_alignments accepted;
                                 * 3 (round 4): mgx_alignment::n_labels / labels_begin, mgx_results::labels (label-aware alignment),
                                 * mgx_stats::extend_kernels / n_lane_reads / lane_ms, "key=value" options of mgx_aligner_set_pipeline;
@@ -305,10 +307,56 @@ int mgx_chain_alignments(const mgx_config *config, uint32_t k, const mgx_results
 void mgx_aligner_keep_seeds(mgx_aligner *a, int keep);
 int mgx_fetch_seed_info(mgx_aligner *a, uint32_t *info6, uint32_t *seeds, uint32_t *max_seeds_out);
 
-/* Hot loop #1 only: map both strands to nodes (dbg_aligner.cpp:210,227-231): map_to_nodes_sequentially of the query and of
- * its reverse complement; on a PRIMARY graph those of the CanonicalDBG wrapper (canonical_dbg.cpp:55-146,551-560). */
+/* Hot loop #1 only: map both strands to nodes (dbg_aligner.cpp:210,227-231): DeBruijnGraph::map_to_nodes_sequentially of the
+ * query and of its reverse complement — what the ALIGNER seeds from; on a PRIMARY graph those of the CanonicalDBG wrapper
+ * (canonical_dbg.cpp:55-146,551-560).  Both node arrays travel to the host.  This is not DeBruijnGraph::map_to_nodes (they
+ * differ on CANONICAL and PRIMARY graphs): for that, and for the counts of `align --map`, see mgx_map_summary_batch. */
 int mgx_map_batch(mgx_aligner *a, const char *seqs, const uint64_t *offsets, uint64_t n_queries,
                   int seqs_on_device, mgx_mapping *out);
+
+/*
+ * `metagraph align --map` (map_sequences_in_file, cli/align.cpp:71-179): DeBruijnGraph::map_to_nodes of every query, summarised
+ * on the device.  Node of k-mer i of a query with n k-mers (a query shorter than k has none):
+ *   BASIC      the forward mapping, node mask applied (dbg_succinct.cpp:484-497)
+ *   CANONICAL  min(forward[i], reverse-complement[n - 1 - i]) over BOSS indexes, 0 if either is missing; the mask after the minimum
+ *              (dbg_succinct.cpp:436-482)
+ *   PRIMARY    the CanonicalDBG wrapper's path (what mgx_map_batch gives) as base nodes: id > n_edges ? id - n_edges : id
+ *              (cli/align.cpp:345-348, canonical_dbg.cpp:148-154)
+ * Counts per query (cli/align.cpp:134-164): non-zero nodes, k-mers, distinct non-zero nodes.
+ * map_length: 0 or k = whole k-mers.  0 < L < k (--align-length L): the query's len - L + 1 windows of the FORWARD strand only,
+ * node = the first one call_nodes_with_suffix_matching_longest_prefix(window, ., L) reports (dbg_succinct.cpp:307-393), 0 if none
+ * or if the window holds a character outside ACGT — BASIC and CANONICAL graphs.  On a PRIMARY graph the reference casts the
+ * CanonicalDBG wrapper it has just built to a DBGSuccinct there (cli/align.cpp:117 after :347), which is undefined behaviour:
+ * MGX_ERR_UNSUPPORTED.  map_length > k: MGX_ERR_INVALID.
+ * Without MGX_MAP_WANT_NODES the only device-to-host traffic of a batch is the 12-byte records (node_begin and nodes are NULL).
+ * Runs on the aligner's stream and honours the graph's mask and the map_pipe= switch like mgx_map_batch.  The views stay valid
+ * until the next batch call on this aligner.
+ */
+typedef struct mgx_map_counts { uint32_t n_discovered, n_kmers, n_unique; } mgx_map_counts;
+typedef struct mgx_map_summary {
+    uint64_t n_queries;
+    const mgx_map_counts *counts;     /* n_queries */
+    const uint64_t *node_begin;       /* n_queries + 1; NULL unless MGX_MAP_WANT_NODES */
+    const uint64_t *nodes;            /* the map_to_nodes result, rules above */
+} mgx_map_summary;
+enum { MGX_MAP_WANT_NODES = 1 };
+int mgx_map_summary_batch(mgx_aligner *a, const char *seqs, const uint64_t *offsets, uint64_t n_queries,
+                          int seqs_on_device, uint32_t map_length /* 0 = k; > k: MGX_ERR_INVALID */,
+                          uint32_t flags, mgx_map_summary *out);
+/* --query-presence, in double exactly as the reference writes it.  map_length 0 or k: DeBruijnGraph::find
+ * (sequence_graph.cpp:65-89): absent if query_len < k, else present iff n_kmers - n_discovered <= (size_t)(n_kmers * (1 - f)).
+ * map_length < k (cli/align.cpp:139-149): present iff n_discovered >= (size_t)(n_kmers - n_kmers * (1 - f)) — a query without a
+ * window is present.  Returns 1 / 0.  Host code, needs no GPU. */
+int mgx_map_present(const mgx_map_counts *c, uint64_t query_len, uint32_t k, uint32_t map_length, double discovery_fraction);
+/* The bytes map_sequences_in_file prints for one query (cli/align.cpp:91-173): MGX_MAP_FMT_NODES "{window}: {node}\n" per window
+ * (needs MGX_MAP_WANT_NODES), _COUNT_KMERS "{header}\t{discovered}/{kmers}/{unique}\n", _QUERY_PRESENCE "0\n" / "1\n",
+ * _FILTER_PRESENT ">{header}\n{query}\n" or nothing.  Same return convention as mgx_format_tsv.  Host code, needs no GPU. */
+enum { MGX_MAP_FMT_NODES = 0, MGX_MAP_FMT_COUNT_KMERS = 1, MGX_MAP_FMT_QUERY_PRESENCE = 2, MGX_MAP_FMT_FILTER_PRESENT = 3 };
+size_t mgx_format_map(const mgx_map_summary *s, uint64_t query_index, const char *header, const char *query, size_t query_len,
+                      uint32_t k, uint32_t map_length, int format, double discovery_fraction, char *buf, size_t buf_len);
+/* Test hook: since the library was loaded, out4[0 .. 2] = launches of k_map_summary's short-read form, of its long-read form and
+ * of k_map_subk; out4[3] = bytes of node arrays mgx_map_summary_batch has copied to the host (0 in counts mode). */
+void mgx_map_kernel_launch_counts(uint64_t *out4);
 
 int mgx_aligner_stats(const mgx_aligner *a, mgx_stats *out);
 /* Test hook: launches of each extension kernel since the library was loaded, out5[b] = the kernel of bit b of MGX_KERNEL_*

@@ -227,6 +227,28 @@ class Aligner:
             out.append(([m.nodes_fwd[i] for i in range(b, e)], [m.nodes_rc[i] for i in range(b, e)]))
         return out
 
+    def map_summary(self, queries, map_length=0, want_nodes=False):
+        """`align --map` (mgx_map_summary_batch): DeBruijnGraph::map_to_nodes of every query summarised on the device.
+        -> list of (n_discovered, n_kmers, n_unique); with want_nodes: (that list, list of node lists).  map_length 0 = k,
+        0 < L < k = the windows of --align-length L.  The view itself is kept in self.last_map_summary for format_map."""
+        blob, offs = pack_queries(queries)
+        m = capi.MapSummary()
+        _check(capi.lib().mgx_map_summary_batch(self.h, blob, offs.ctypes.data, len(queries), 0, map_length,
+                                                capi.MGX_MAP_WANT_NODES if want_nodes else 0, C.byref(m)))
+        self.last_map_summary = m
+        counts = [(m.counts[q].n_discovered, m.counts[q].n_kmers, m.counts[q].n_unique) for q in range(len(queries))]
+        if not want_nodes:
+            return counts
+        nb = np.ctypeslib.as_array(m.node_begin, shape=(len(queries) + 1,))
+        nodes = np.ctypeslib.as_array(m.nodes, shape=(max(1, int(nb[-1])),))
+        return counts, [nodes[int(nb[q]):int(nb[q + 1])].tolist() for q in range(len(queries))]
+
+    def map_present(self, counts, query_len, map_length=0, discovery_fraction=0.7):
+        return map_present(counts, query_len, self.graph.k, map_length, discovery_fraction)
+
+    def format_map(self, summary, qi, header, query, fmt, map_length=0, discovery_fraction=0.7):
+        return format_map(summary, qi, header, query, self.graph.k, fmt, map_length, discovery_fraction)
+
     def set_pipeline(self, name):
         """Kernel selection: 'split8' (the name of the one pipeline: accepted, selects nothing), 'general' / 'chain'
         (extension chain path off / on), 'key=value' options (include/mgx.h lists them at mgx_aligner_set_pipeline);
@@ -259,3 +281,19 @@ class Aligner:
         buf = C.create_string_buffer(n + 1)
         capi.lib().mgx_format_tsv(C.byref(res), qi, header.encode(), q, len(q), cfg.min_path_score, buf, n + 1)
         return buf.value.decode("latin-1")
+
+
+def map_present(counts, query_len, k, map_length=0, discovery_fraction=0.7):
+    """mgx_map_present (host only): --query-presence of one query from its (n_discovered, n_kmers, n_unique)."""
+    c = capi.MapCounts(*counts)
+    return bool(capi.lib().mgx_map_present(C.byref(c), query_len, k, map_length, discovery_fraction))
+
+
+def format_map(summary, qi, header, query, k, fmt, map_length=0, discovery_fraction=0.7):
+    """mgx_format_map (host only): the bytes `metagraph align --map` prints for query qi of a capi.MapSummary; fmt = capi.MGX_MAP_FMT_*."""
+    q = query if isinstance(query, bytes) else query.encode("latin-1")
+    args = (C.byref(summary), qi, header.encode(), q, len(q), k, map_length, fmt, discovery_fraction)
+    n = capi.lib().mgx_format_map(*args, None, 0)
+    buf = C.create_string_buffer(n + 1)
+    capi.lib().mgx_format_map(*args, buf, n + 1)
+    return buf.value.decode("latin-1")

@@ -71,6 +71,19 @@ class Mapping(C.Structure):
                 ("nodes_fwd", C.POINTER(C.c_uint64)), ("nodes_rc", C.POINTER(C.c_uint64))]
 
 
+class MapCounts(C.Structure):
+    _fields_ = [("n_discovered", C.c_uint32), ("n_kmers", C.c_uint32), ("n_unique", C.c_uint32)]
+
+
+class MapSummary(C.Structure):
+    _fields_ = [("n_queries", C.c_uint64), ("counts", C.POINTER(MapCounts)),
+                ("node_begin", C.POINTER(C.c_uint64)), ("nodes", C.POINTER(C.c_uint64))]
+
+
+MGX_MAP_WANT_NODES = 1
+MGX_MAP_FMT_NODES, MGX_MAP_FMT_COUNT_KMERS, MGX_MAP_FMT_QUERY_PRESENCE, MGX_MAP_FMT_FILTER_PRESENT = 0, 1, 2, 3
+
+
 class Stats(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_rank_lines", C.c_uint64), ("n_select_lines", C.c_uint64),
                 ("n_bit_lines", C.c_uint64), ("n_columns", C.c_uint64), ("n_extensions", C.c_uint64),
@@ -259,6 +272,14 @@ def lib():
     L.mgx_gather_start.argtypes = [C.c_void_p, C.c_void_p]
     L.mgx_gather_finish.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.mgx_map_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(Mapping)]
+    L.mgx_map_summary_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32,
+                                        C.POINTER(MapSummary)]
+    L.mgx_map_present.argtypes = [C.POINTER(MapCounts), C.c_uint64, C.c_uint32, C.c_uint32, C.c_double]
+    L.mgx_format_map.argtypes = [C.POINTER(MapSummary), C.c_uint64, C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                 C.c_int, C.c_double, C.c_char_p, C.c_size_t]
+    L.mgx_format_map.restype = C.c_size_t
+    L.mgx_map_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_map_kernel_launch_counts.restype = None
     L.mgx_aligner_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.mgx_config_init_default.argtypes = [C.POINTER(Config)]
     L.mgx_config_init_cli.argtypes = [C.POINTER(Config), C.c_uint32]

@@ -12,6 +12,7 @@
 constexpr size_t MGX_ALIGN_PARAMS_BYTES = 728;          // sizeof(AlignParams), align_types.hpp
 constexpr size_t MGX_LANE_PARAMS_BYTES = 848;           // sizeof(LaneParams), lane_types.hpp
 constexpr size_t MGX_SEED_LANE_PARAMS_BYTES = 824;      // sizeof(SeedLaneParams), seed_lane.hpp
+constexpr size_t MGX_DEV_GRAPH_BYTES = 160;             // sizeof(DevGraph), dev_graph.hpp
 
 struct mgx_annotation;
 
@@ -56,6 +57,17 @@ int mgx_lane_waves_per_simd(void);
 // more than SL_SHORT_L characters
 int mgx_launch_seed_lane(const void *d_params, uint32_t blocks, int long_reads, void *stream);
 int mgx_seed_lane_waves_per_simd(void);
+
+// mgx_mapsum.hip: the per-read counts of `align --map` (map_summary.hpp).  counts: n_reads records of 12 bytes (mgx_map_counts);
+// out_nodes: the merged node array or null; sorted: the long form's scratch (a word per k-mer of the batch); long_form selects
+// the build for reads of more than mgx_map_summary_short_max() k-mers — each launch takes the reads of its form only.
+// mgx_launch_map_subk: nodes[node_begin[r] + i] = the node of window i (map_length characters) of read r; dev_graph: a DevGraph.
+int mgx_launch_map_summary(const uint64_t *node_begin, const uint32_t *fwd, const uint32_t *rc, uint32_t *sorted, void *counts,
+                           uint64_t *out_nodes, const uint64_t *valid, uint64_t n_reads, uint32_t n_edges, int mode, int long_form,
+                           void *stream);
+int mgx_launch_map_subk(const void *dev_graph, const char *seqs, const uint64_t *offsets, const uint64_t *node_begin, uint32_t *nodes,
+                        uint64_t n_reads, uint32_t map_length, void *stream);
+uint32_t mgx_map_summary_short_max(void);
 
 // mgx_annot.hip: the matrix as the label-aware extension kernels read it (AlignParams::anno_*), and the annotation's
 // process-unique id

@@ -596,6 +596,9 @@ struct mgx_aligner {
     uint64_t aligned_generation = 0;             // ... and which of them mgx_align_batch_device aligned: post-chaining and the
                                                  // capacity retry read the batch back only while it is still the staged one
     std::vector<uint64_t> m_node_begin, m_fwd, m_rc;
+    DevBuf ms_counts, ms_nodes, ms_sorted;       // mgx_map_summary_batch: the 12-byte records, the merged node array, the long form's scratch
+    std::vector<mgx_map_counts> h_ms_counts;
+    std::vector<uint64_t> h_ms_nodes;
     mgx_stats hstats;
     hipEvent_t ev[EV_COUNT] = {};
     uint64_t kernels_ran = 0;     // MGX_KERNEL_* bits of the extension kernels the last batch launched
@@ -904,7 +907,7 @@ static int aligner_create(const mgx_graph *g, const mgx_config *config, const mg
                        &A->cursors, &A->d_stats, &A->d_stats_map, &A->scan_tmp, &A->dbg_seeds, &A->seed_hdr, &A->seed_stream, &A->work_key,
                        &A->work_key_sorted, &A->order_in, &A->order, &A->sort_tmp, &A->retry_list, &A->resume_pool[0], &A->resume_pool[1],
                        &A->retry_list2, &A->retry_key[0], &A->retry_key[1], &A->lane_scratch, &A->lane_params, &A->lane_bail, &A->lane_hist, &A->seedlane_scratch, &A->seedlane_params,
-                       &A->seedlane_bail, &A->seedlane_hist })
+                       &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted })
         b->pooled = true;
     {
         std::string err;
@@ -1007,9 +1010,10 @@ static hipError_t copy_sync(mgx_aligner *A, void *dst, const void *src, size_t b
 }
 
 // stage inputs, compute k-mer slot offsets and Lmax on the device
+// (window: the characters per node slot — the graph's k, or mgx_map_summary_batch's map_length < k)
 static int stage_batch(mgx_aligner *A, const char *seqs, const uint64_t *offsets, uint64_t n, int on_device,
-                       const char **d_seqs, const uint64_t **d_offsets, uint32_t *Lmax_out) {
-    const uint32_t k = A->graph->g.k;
+                       const char **d_seqs, const uint64_t **d_offsets, uint32_t *Lmax_out, uint32_t window = 0) {
+    const uint32_t k = window ? window : A->graph->g.k;
     ++A->stage_generation;
     if (on_device) {
         *d_seqs = seqs;
@@ -1058,7 +1062,11 @@ static int stage_batch(mgx_aligner *A, const char *seqs, const uint64_t *offsets
     return MGX_OK;
 }
 
-static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, bool do_rc, bool mapped, uint32_t Lmax) {
+// raw_edges: BOSS::map_to_edges, the node mask not applied (mgx_map_summary_batch on CANONICAL graphs applies it after the minimum)
+static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, bool do_rc, bool mapped, uint32_t Lmax,
+                   bool raw_edges = false) {
+    DevGraph dg = A->graph->g;
+    if (raw_edges) dg.valid = nullptr;
     // k_map's counters live in their own block: a re-run of the alignment stage (stream overflow) resets only its own
     HIP_TRY(hipMemsetAsync(A->d_stats_map.p, 0, sizeof(KernelStats), A->hstream));
     HIP_TRY(hipMemsetAsync(A->d_stats.p, 0, sizeof(KernelStats), A->hstream));
@@ -1109,9 +1117,9 @@ static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets
                 ma.min_rng_len = (int32_t)std::min<uint64_t>(A->cfg.min_seed_length, 1u << 20);
                 ma.n_reads = n; ma.do_rc = do_rc ? 1 : 0; ma.cursor = map_cursor;
                 const uint64_t pblocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)prop.multiProcessorCount * MGX_MAP_PIPE_WAVES, (chains + 255) / 256));
-                k_map_pipe<<<(uint32_t)pblocks, 256, 0, A->hstream>>>(A->graph->g, ma, A->d_stats_map.as<KernelStats>());
+                k_map_pipe<<<(uint32_t)pblocks, 256, 0, A->hstream>>>(dg, ma, A->d_stats_map.as<KernelStats>());
             } else
-            k_map_packed<<<(uint32_t)blocks, 256, 0, A->hstream>>>(A->graph->g, d_offsets, A->node_begin.as<uint64_t>(),
+            k_map_packed<<<(uint32_t)blocks, 256, 0, A->hstream>>>(dg, d_offsets, A->node_begin.as<uint64_t>(),
                                          A->pk_fwd.as<uint64_t>(), A->pk_rc.as<uint64_t>(), A->iv_fwd.as<uint32_t>(), A->iv_rc.as<uint32_t>(),
                                          A->nodes_fwd.as<uint32_t>(), A->nodes_rc.as<uint32_t>(),
                                          A->mlen_fwd.as<uint8_t>(), A->mlen_rc.as<uint8_t>(),
@@ -1119,7 +1127,7 @@ static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets
                                          (int)std::min<uint64_t>(A->cfg.min_seed_length, 1u << 20), n, do_rc ? 1 : 0,
                                          map_cursor, A->d_stats_map.as<KernelStats>());
         } else {
-            k_map<<<(uint32_t)blocks, 256, 0, A->hstream>>>(A->graph->g, d_seqs, d_offsets, A->node_begin.as<uint64_t>(),
+            k_map<<<(uint32_t)blocks, 256, 0, A->hstream>>>(dg, d_seqs, d_offsets, A->node_begin.as<uint64_t>(),
                                          A->nodes_fwd.as<uint32_t>(), A->nodes_rc.as<uint32_t>(),
                                          A->mlen_fwd.as<uint8_t>(), A->mlen_rc.as<uint8_t>(),
                                          A->have_rng ? A->rng_fwd.as<uint2>() : nullptr, A->have_rng ? A->rng_rc.as<uint2>() : nullptr,
@@ -1129,7 +1137,7 @@ static int run_map(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets
     }
     HIP_TRY(hipGetLastError());
     if (A->graph->mode == MGX_MODE_PRIMARY && do_rc && n) {
-        k_canon_merge<<<(uint32_t)std::min<uint64_t>((n + 3) / 4, 65536), 256, 0, A->hstream>>>(A->graph->g, d_seqs, d_offsets, A->node_begin.as<uint64_t>(),
+        k_canon_merge<<<(uint32_t)std::min<uint64_t>((n + 3) / 4, 65536), 256, 0, A->hstream>>>(dg, d_seqs, d_offsets, A->node_begin.as<uint64_t>(),
                                                                              A->nodes_fwd.as<uint32_t>(), A->nodes_rc.as<uint32_t>(), n);
         HIP_TRY(hipGetLastError());
     }
@@ -1706,6 +1714,66 @@ int mgx_map_batch(mgx_aligner *A, const char *seqs, const uint64_t *offsets, uin
     out->nodes_rc = A->m_rc.data();
     return MGX_OK;
 }
+
+// `align --map` (cli/align.cpp:71-179): DeBruijnGraph::map_to_nodes summarised on the device (map_summary.hpp, mgx_mapsum.hip)
+static std::atomic<uint64_t> g_map_summary_counts[4];        // mgx_map_kernel_launch_counts
+int mgx_map_summary_batch(mgx_aligner *A, const char *seqs, const uint64_t *offsets, uint64_t n, int on_device, uint32_t map_length,
+                          uint32_t flags, mgx_map_summary *out) {
+    if (!A || !seqs || !offsets || !out) return fail(MGX_ERR_INVALID, "null argument");
+    const uint32_t k = A->graph->g.k;
+    if (map_length > k) return fail(MGX_ERR_INVALID, "map_length %u exceeds k = %u", map_length, k);
+    if (flags & ~(uint32_t)MGX_MAP_WANT_NODES) return fail(MGX_ERR_INVALID, "unknown flags %u", flags);
+    const bool sub_k = map_length != 0 && map_length < k;
+    const uint32_t mode = A->graph->mode;
+    // the reference casts the CanonicalDBG wrapper to a DBGSuccinct here (cli/align.cpp:117 after :347): undefined, so refused
+    if (sub_k && mode == MGX_MODE_PRIMARY) return fail(MGX_ERR_UNSUPPORTED, "map_length < k on a PRIMARY graph is undefined in the reference");
+    if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
+    HIP_TRY(hipSetDevice(A->graph->device));
+    const char *d_seqs; const uint64_t *d_offsets; uint32_t Lmax;
+    if (int rc = stage_batch(A, seqs, offsets, n, on_device, &d_seqs, &d_offsets, &Lmax, sub_k ? map_length : 0)) return rc;
+    const bool want_nodes = (flags & MGX_MAP_WANT_NODES) != 0;
+    const uint32_t window = sub_k ? map_length : k;
+    const bool any_long = Lmax >= window && Lmax - window + 1 > mgx_map_summary_short_max();
+    if (int rc = A->ms_counts.ensure((n + 1) * sizeof(mgx_map_counts))) return rc;
+    if (want_nodes) if (int rc = A->ms_nodes.ensure((A->total_kmers + 1) * 8)) return rc;
+    if (any_long) if (int rc = A->ms_sorted.ensure((A->total_kmers + 1) * 4)) return rc;
+    int rule = MGX_MODE_BASIC;
+    if (sub_k) {
+        if (mgx_launch_map_subk(&A->graph->g, d_seqs, d_offsets, A->node_begin.as<uint64_t>(), A->nodes_fwd.as<uint32_t>(), n, map_length, A->hstream))
+            return fail(MGX_ERR_NO_DEVICE, "k_map_subk launch failed");
+        if (n) ++g_map_summary_counts[2];
+    } else {
+        // BASIC: the forward strand alone.  CANONICAL: both strands' BOSS edges, the mask after the minimum.  PRIMARY: the wrapper's path.
+        rule = (int)mode;
+        if (int rc = run_map(A, d_seqs, d_offsets, n, mode != MGX_MODE_BASIC, true, Lmax, mode == MGX_MODE_CANONICAL)) return rc;
+    }
+    for (int long_form = 0; long_form <= (any_long ? 1 : 0); ++long_form) {
+        if (mgx_launch_map_summary(A->node_begin.as<uint64_t>(), A->nodes_fwd.as<uint32_t>(), A->nodes_rc.as<uint32_t>(), A->ms_sorted.as<uint32_t>(),
+                                   A->ms_counts.p, want_nodes ? A->ms_nodes.as<uint64_t>() : nullptr, A->graph->g.valid, n,
+                                   (uint32_t)A->graph->g.n, rule, long_form, A->hstream))
+            return fail(MGX_ERR_NO_DEVICE, "k_map_summary launch failed");
+        if (n) ++g_map_summary_counts[long_form];
+    }
+    if (!sub_k) { if (int rc = collect_stats(A, true, false)) return rc; }
+    A->h_ms_counts.resize(n);
+    if (n) HIP_TRY(copy_sync(A, A->h_ms_counts.data(), A->ms_counts.p, n * sizeof(mgx_map_counts), hipMemcpyDeviceToHost));
+    else HIP_TRY(hipStreamSynchronize(A->hstream));
+    out->n_queries = n;
+    out->counts = A->h_ms_counts.data();
+    out->node_begin = nullptr;
+    out->nodes = nullptr;
+    if (want_nodes) {
+        A->m_node_begin.resize(n + 1);
+        HIP_TRY(copy_sync(A, A->m_node_begin.data(), A->node_begin.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+        A->h_ms_nodes.resize(A->total_kmers + 1);
+        if (A->total_kmers) HIP_TRY(copy_sync(A, A->h_ms_nodes.data(), A->ms_nodes.p, A->total_kmers * 8, hipMemcpyDeviceToHost));
+        g_map_summary_counts[3] += A->total_kmers * 8;
+        out->node_begin = A->m_node_begin.data();
+        out->nodes = A->h_ms_nodes.data();
+    }
+    return MGX_OK;
+}
+void mgx_map_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_map_summary_counts[x].load(); }
 
 // the device blocks kept from destroyed aligners (DevPool) go back to the driver
 int mgx_device_trim(int device) {

@@ -155,6 +155,51 @@ class HipGraphSet {
     std::vector<std::unique_ptr<HipBOSSGraph>> replicas_;
 };
 
+// DeBruijnGraph::map_to_nodes / DeBruijnGraph::find on the device graph — the graph-side calls behind `metagraph align --map`
+// (map_sequences_in_file, cli/align.cpp:71-179).  Holds a device handle of its own; one per worker thread.  The batched form is
+// the one to use: a single sequence pays a whole launch.
+class HipGraphMapper {
+  public:
+    explicit HipGraphMapper(const HipBOSSGraph &graph) : graph_(graph) {
+        mgx_config cfg;
+        mgx_config_init_cli(&cfg, (uint32_t)graph.get_k());
+        if (int rc = mgx_aligner_create(graph.handle(), &cfg, nullptr, &a_))
+            throw std::runtime_error(std::string(mgx_last_error()) + " (" + std::to_string(rc) + ")");
+    }
+    ~HipGraphMapper() { mgx_aligner_destroy(a_); }
+    HipGraphMapper(const HipGraphMapper &) = delete;
+    // The view of the whole batch (valid until the next call): counts per sequence and, with want_nodes, the node arrays.
+    // map_length: 0 = k; L < k = the windows of --align-length L (BASIC and CANONICAL graphs).
+    mgx_map_summary map_batch(const std::vector<std::string_view> &seqs, uint32_t map_length = 0, bool want_nodes = false) const {
+        std::string blob;
+        std::vector<uint64_t> offsets(seqs.size() + 1, 0);
+        for (size_t t = 0; t < seqs.size(); ++t) { blob.append(seqs[t].data(), seqs[t].size()); offsets[t + 1] = blob.size(); }
+        if (blob.empty()) blob.push_back('\0');
+        mgx_map_summary out{};
+        if (int rc = mgx_map_summary_batch(a_, blob.data(), offsets.data(), seqs.size(), 0, map_length, want_nodes ? MGX_MAP_WANT_NODES : 0, &out))
+            throw std::runtime_error(std::string("mgx_map_summary_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        return out;
+    }
+    // std::vector<node_index> map_to_nodes(const DeBruijnGraph &, std::string_view) (sequence_graph.cpp)
+    std::vector<uint64_t> map_to_nodes(std::string_view sequence) const {
+        const mgx_map_summary s = map_batch({ sequence }, 0, true);
+        return std::vector<uint64_t>(s.nodes + s.node_begin[0], s.nodes + s.node_begin[1]);
+    }
+    // bool DeBruijnGraph::find(std::string_view sequence, double discovery_fraction = 1) (sequence_graph.cpp:65-89)
+    bool find(std::string_view sequence, double discovery_fraction = 1) const {
+        const mgx_map_summary s = map_batch({ sequence });
+        return mgx_map_present(&s.counts[0], sequence.size(), (uint32_t)graph_.get_k(), 0, discovery_fraction) != 0;
+    }
+    void set_kernel_option(const std::string &opt) {
+        if (int rc = mgx_aligner_set_pipeline(a_, opt.c_str()))
+            throw std::runtime_error(std::string(mgx_last_error()) + " (" + std::to_string(rc) + ")");
+    }
+    const HipBOSSGraph &get_graph() const { return graph_; }
+  private:
+    const HipBOSSGraph &graph_;
+    mgx_aligner *a_ = nullptr;
+};
+
 class IDBGAligner {
   public:
     typedef std::pair<std::string /* header */, std::string /* seq */> Query;

@@ -4,6 +4,12 @@
 //   mgx_align GRAPH.{dbg,boss} READS.{fa,fq} [--align-only-forwards] [--align-min-exact-match X] [--align-min-seed-length N]
 //             [-p THREADS] [--query-batch-size BASES] [--canonical | --primary (the dump is a CANONICAL- / PRIMARY-mode graph)]
 //             [--time]        wall time of the align loop on stderr
+//             [--map]         map_sequences_in_file (cli/align.cpp:71-179) instead of aligning: "{k-mer}: {node}" per k-mer, or with
+//                             --count-kmers "{name}\t{discovered}/{k-mers}/{distinct}", --query-presence "0" / "1",
+//                             --query-presence --filter-present the present records as FASTA; --discovery-fraction X (0.7);
+//                             --align-length N (windows of N < k characters; 0 = k, above k: a warning and k);
+//                             --fwd-and-reverse (every record followed by its reverse complement under the same name).
+//                             Output in input order; no annotation is loaded in this mode
 //             [--devices D]   in-process multi-GPU: one graph replica per device, whole batches routed round-robin, no collective
 //             [--rccl-gather] with --devices D: one worker per device, batches in rounds of D; every round's device results are
 //                             gathered to device 0 over RCCL (mgx_gather_*: the C-ABI of north_star's "RCCL-over-xGMI only to
@@ -102,8 +108,18 @@ int main(int argc, char **argv) {
     bool rccl_gather = false;
     std::vector<const char *> anno_paths;
     std::vector<std::string> kernel_options;            // --kernel-option key=value: result-preserving kernel selection (A/B runs)
+    bool map_mode = false, count_kmers = false, query_presence = false, filter_present = false, fwd_and_reverse = false;
+    double discovery_fraction = 0.7;                     // cli/config/config.hpp:136
+    uint32_t align_length = 0;
     mgx_limits_init_default(&lim, 0);
     for (int i = 3; i < argc; ++i) {
+        if (!strcmp(argv[i], "--map")) { map_mode = true; continue; }
+        if (!strcmp(argv[i], "--count-kmers")) { count_kmers = true; continue; }
+        if (!strcmp(argv[i], "--query-presence")) { query_presence = true; continue; }
+        if (!strcmp(argv[i], "--filter-present")) { filter_present = true; continue; }
+        if (!strcmp(argv[i], "--fwd-and-reverse")) { fwd_and_reverse = true; continue; }
+        if (!strcmp(argv[i], "--discovery-fraction") && i + 1 < argc) { discovery_fraction = atof(argv[++i]); continue; }
+        if (!strcmp(argv[i], "--align-length") && i + 1 < argc) { align_length = (uint32_t)std::max(0, atoi(argv[++i])); continue; }
         if (!strcmp(argv[i], "--align-only-forwards")) cfg.forward_and_reverse_complement = 0;
         else if (!strcmp(argv[i], "--align-min-exact-match") && i + 1 < argc) cfg.min_exact_match = atof(argv[++i]);
         else if (!strcmp(argv[i], "--align-min-seed-length") && i + 1 < argc) cfg.min_seed_length = std::min<uint64_t>(atoi(argv[++i]), k);
@@ -118,6 +134,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--canonical")) graph_mode = MGX_MODE_CANONICAL;
         else if (!strcmp(argv[i], "--primary")) graph_mode = MGX_MODE_PRIMARY;         // aligned through the CanonicalDBG wrapper
     }
+    if (map_mode) anno_paths.clear();                    // no annotation is loaded in this mode (cli/align.cpp:316-318)
     try {
         // one replica of the index per device (3.5 B/edge + the suffix-range table each); more devices than the box shows is an
         // error of the caller's, reported like any other
@@ -166,6 +183,49 @@ int main(int argc, char **argv) {
         if ((unsigned)devices > threads) threads = (unsigned)devices;                  // at least one worker per device
         std::vector<IDBGAligner::Query> all;
         if (!read_records(argv[2], &all)) { fprintf(stderr, "cannot open %s\n", argv[2]); return 1; }
+        if (map_mode) {
+            // cli/align.cpp:351-355
+            if (align_length > k) { fprintf(stderr, "warning: Mapping to k-mers longer than k is not supported. Setting --align-length to %u\n", k); align_length = k; }
+            if (!align_length) align_length = k;
+            if (fwd_and_reverse) {                      // sequence_io.hpp:317-319
+                std::vector<IDBGAligner::Query> both;
+                for (auto &q : all) {
+                    std::string rc(q.second.rbegin(), q.second.rend());
+                    for (char &c : rc)
+                        switch (c) {
+                            case 'A': c = 'T'; break; case 'C': c = 'G'; break; case 'G': c = 'C'; break; case 'T': c = 'A'; break;
+                            case 'a': c = 't'; break; case 'c': c = 'g'; break; case 'g': c = 'c'; break; case 't': c = 'a'; break;
+                            default: break;
+                        }
+                    both.push_back(q);
+                    both.emplace_back(q.first, std::move(rc));
+                }
+                all.swap(both);
+            }
+            const int format = query_presence ? (filter_present ? MGX_MAP_FMT_FILTER_PRESENT : MGX_MAP_FMT_QUERY_PRESENCE)
+                               : count_kmers ? MGX_MAP_FMT_COUNT_KMERS : MGX_MAP_FMT_NODES;
+            HipGraphMapper mapper(graphs.for_worker(0));
+            for (const std::string &opt : kernel_options) mapper.set_kernel_option(opt);
+            std::string line;
+            for (size_t i = 0; i < all.size();) {
+                const size_t first = i;
+                std::vector<std::string_view> seqs;
+                uint64_t bytes = 0;
+                for (; i < all.size() && bytes <= batch_size; ++i) { bytes += all[i].second.size(); seqs.emplace_back(all[i].second); }
+                const mgx_map_summary s = mapper.map_batch(seqs, align_length, format == MGX_MAP_FMT_NODES);
+                for (size_t t = 0; t < seqs.size(); ++t) {
+                    const IDBGAligner::Query &q = all[first + t];
+                    const size_t need = mgx_format_map(&s, t, q.first.c_str(), q.second.data(), q.second.size(), k, align_length, format,
+                                                       discovery_fraction, nullptr, 0);
+                    line.resize(need + 1);
+                    mgx_format_map(&s, t, q.first.c_str(), q.second.data(), q.second.size(), k, align_length, format, discovery_fraction,
+                                   line.data(), need + 1);
+                    std::cout.write(line.data(), (std::streamsize)need);
+                }
+            }
+            std::cout.flush();
+            return 0;
+        }
         // batches by bases read (align.cpp:431-442: a record is added while the running total is <= batch_size)
         std::vector<std::vector<IDBGAligner::Query>> batches;
         const size_t n_queries = all.size();
