@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_map_summary_batch / mgx_map_present / mgx_format_map / mgx_map_kernel_launch_counts
+#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_format_tsv_batch / mgx_format_kernel_launch_counts (the TSV text of a batch, written
+                                * by kernels); before that mgx_map_summary_batch / mgx_map_present / mgx_format_map / mgx_map_kernel_launch_counts
                                 * (`align --map`: per-read k-mer counts, presence, --align-length < k);
                                 * 6 (round 6, late): mgx_gather_* (RCCL gather of the device results); 5 (round 6): mgx_stats::n_seed_lane_reads / seed_lane_ms / seed_lane_left_reads, streams, coordinates,
                                 * mgx_chain_seeds; 4 (round 5): mgx_stats::n_capacity_retried, mgx_chain_alignments, post_chain_alignments accepted;
@@ -532,6 +533,36 @@ int mgx_labeled_aligner_create(const mgx_graph *graph, const mgx_config *config,
 size_t mgx_format_tsv_labeled(const mgx_results *res, uint64_t query_index, const char *header,
                               const char *query, size_t query_len, int32_t min_path_score,
                               const char *const *label_names, uint32_t n_label_names, char *buf, size_t buf_len);
+/*
+ * The TSV text of a whole batch, written on the device (csrc/tsv_format.hpp, csrc/mgx_format.hip).
+ * After mgx_align_batch_device (or mgx_align_batch) on this handle: what format_alignment (cli/align.cpp:254-285) prints for
+ * every query of the batch, byte for byte what mgx_format_tsv_labeled gives query by query.  headers: the concatenated header
+ * bytes, header i = headers[header_offsets[i] .. header_offsets[i + 1]) (host arrays, n_queries + 1 offsets).  label_names /
+ * n_label_names as in mgx_format_tsv_labeled (NULL / 0: numbers; only a label-aware aligner prints labels); the names are
+ * uploaded with every call.  min_path_score is the aligner's config's.  The views are host memory owned by the handle and stay
+ * valid until the next batch or format call on it.
+ *   - Runs on the aligner's stream.  Device-to-host copies: the text, the n_queries + 1 offsets and 16 bytes of counters
+ *     (the text's size, the number of capacity-status records); the result records and the stream do not travel.
+ *   - Capacity statuses (the device records are pre-retry): those queries alone go through the retry mgx_fetch_results
+ *     performs; their lines come from mgx_format_tsv_labeled on the retried results and stand at their place in the text.
+ *     The query numbers and the reads of those queries travel in addition.  The text is complete or the call fails:
+ *     MGX_ERR_CAPACITY, naming the first such query in mgx_last_error, with retry_capacity=0 or when the retry cures none.
+ *   - post_chain_alignments: MGX_ERR_UNSUPPORTED (the chained alignments exist on the host only: mgx_fetch_results +
+ *     mgx_format_tsv remain the path for that configuration).
+ *   - The batch must still be the staged one (no mgx_map_batch / mgx_map_summary_batch on the handle in between), and with
+ *     seqs_on_device != 0 the caller's seqs / offsets must stay valid until the call returns — as for mgx_fetch_results.
+ */
+typedef struct mgx_text {
+    uint64_t n_queries;
+    const char *text;            /* all lines, query order, no NUL */
+    const uint64_t *line_begin;  /* n_queries + 1 byte offsets into text */
+} mgx_text;
+int mgx_format_tsv_batch(mgx_aligner *a, const char *headers, const uint64_t *header_offsets,
+                         const char *const *label_names, uint32_t n_label_names, mgx_text *out);
+/* Test hook: out4 = launches of the size kernel, launches of the write kernel, queries whose line was formatted on the host
+ * (capacity retries), bytes copied device-to-host by mgx_format_tsv_batch — since the library was loaded. */
+void mgx_format_kernel_launch_counts(uint64_t *out4);
+
 /* mgx_results_from_raw for the records of a label-aware aligner (labeled != 0: every alignment's arrays are followed by
  * its label list in the stream). */
 int mgx_results_from_raw_labeled(const void *headers, uint64_t n_queries, const uint32_t *stream, uint64_t stream_words,

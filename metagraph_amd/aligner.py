@@ -282,6 +282,31 @@ class Aligner:
         capi.lib().mgx_format_tsv(C.byref(res), qi, header.encode(), q, len(q), cfg.min_path_score, buf, n + 1)
         return buf.value.decode("latin-1")
 
+    def format_tsv_batch(self, headers, label_names=None):
+        """mgx_format_tsv_batch: the TSV text of the batch align_device / align_batch ran last, written by kernels.
+        headers: one str / bytes per query; label_names: names of labels 0 .. len - 1 (label-aware aligners; others print as
+        numbers).  -> (bytes of all lines in query order, numpy uint64 array of len(headers) + 1 line offsets)."""
+        hs = [h if isinstance(h, bytes) else h.encode("latin-1") for h in headers]
+        hoff = np.zeros(len(hs) + 1, dtype=np.uint64)
+        if hs:
+            hoff[1:] = np.cumsum([len(h) for h in hs])
+        names = [n if isinstance(n, bytes) else n.encode() for n in (label_names or [])]
+        arr = (C.c_char_p * len(names))(*names) if names else None
+        t = capi.Text()
+        _check(capi.lib().mgx_format_tsv_batch(self.h, b"".join(hs), hoff.ctypes.data, arr, len(names), C.byref(t)))
+        if t.n_queries != len(hs):
+            raise ValueError("format_tsv_batch: %d headers for a batch of %d queries" % (len(hs), t.n_queries))
+        lb = np.ctypeslib.as_array(t.line_begin, shape=(len(hs) + 1,)).copy()
+        return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+
+
+def format_kernel_launch_counts():
+    """mgx_format_kernel_launch_counts -> (size kernel launches, write kernel launches, host-formatted lines, bytes copied
+    device-to-host by format_tsv_batch) since the library was loaded"""
+    out = (C.c_uint64 * 4)()
+    capi.lib().mgx_format_kernel_launch_counts(out)
+    return tuple(int(x) for x in out)
+
 
 def map_present(counts, query_len, k, map_length=0, discovery_fraction=0.7):
     """mgx_map_present (host only): --query-presence of one query from its (n_discovered, n_kmers, n_unique)."""

@@ -80,6 +80,11 @@ class MapSummary(C.Structure):
                 ("node_begin", C.POINTER(C.c_uint64)), ("nodes", C.POINTER(C.c_uint64))]
 
 
+class Text(C.Structure):
+    """mgx_text: the TSV text of a batch (mgx_format_tsv_batch)"""
+    _fields_ = [("n_queries", C.c_uint64), ("text", C.c_void_p), ("line_begin", C.POINTER(C.c_uint64))]
+
+
 MGX_MAP_WANT_NODES = 1
 MGX_MAP_FMT_NODES, MGX_MAP_FMT_COUNT_KMERS, MGX_MAP_FMT_QUERY_PRESENCE, MGX_MAP_FMT_FILTER_PRESENT = 0, 1, 2, 3
 
@@ -280,6 +285,9 @@ def lib():
     L.mgx_format_map.restype = C.c_size_t
     L.mgx_map_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.mgx_map_kernel_launch_counts.restype = None
+    L.mgx_format_tsv_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Text)]
+    L.mgx_format_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_format_kernel_launch_counts.restype = None
     L.mgx_aligner_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.mgx_config_init_default.argtypes = [C.POINTER(Config)]
     L.mgx_config_init_cli.argtypes = [C.POINTER(Config), C.c_uint32]

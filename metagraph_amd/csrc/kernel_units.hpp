@@ -13,6 +13,7 @@ constexpr size_t MGX_ALIGN_PARAMS_BYTES = 728;          // sizeof(AlignParams), 
 constexpr size_t MGX_LANE_PARAMS_BYTES = 848;           // sizeof(LaneParams), lane_types.hpp
 constexpr size_t MGX_SEED_LANE_PARAMS_BYTES = 824;      // sizeof(SeedLaneParams), seed_lane.hpp
 constexpr size_t MGX_DEV_GRAPH_BYTES = 160;             // sizeof(DevGraph), dev_graph.hpp
+constexpr size_t MGX_FORMAT_ARGS_BYTES = 128;           // sizeof(TfBatch), tsv_format.hpp
 
 struct mgx_annotation;
 
@@ -68,6 +69,13 @@ int mgx_launch_map_summary(const uint64_t *node_begin, const uint32_t *fwd, cons
 int mgx_launch_map_subk(const void *dev_graph, const char *seqs, const uint64_t *offsets, const uint64_t *node_begin, uint32_t *nodes,
                         uint64_t n_reads, uint32_t map_length, void *stream);
 uint32_t mgx_map_summary_short_max(void);
+
+// mgx_format.hip: the TSV text of a batch (tsv_format.hpp).  args: a TfBatch (host memory).  size: line_len[q] for every query, and
+// the capacity-status queries into cap_list / cap_count; write: the lines at text + line_begin[q]; patch: line_len[queries[i]] =
+// lens[i] for the m lines the host formatted (device arrays).
+int mgx_launch_format_size(const void *args, void *stream);
+int mgx_launch_format_write(const void *args, void *stream);
+int mgx_launch_format_patch(uint64_t *line_len, const uint32_t *queries, const uint64_t *lens, uint32_t m, void *stream);
 
 // mgx_annot.hip: the matrix as the label-aware extension kernels read it (AlignParams::anno_*), and the annotation's
 // process-unique id

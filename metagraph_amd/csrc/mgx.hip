@@ -26,6 +26,7 @@
 #include "lane_types.hpp"
 #include "seed_lane.hpp"
 #include "kernel_units.hpp"
+#include "tsv_format.hpp"
 
 using namespace mgx;
 static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES && sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES
@@ -599,6 +600,12 @@ struct mgx_aligner {
     DevBuf ms_counts, ms_nodes, ms_sorted;       // mgx_map_summary_batch: the 12-byte records, the merged node array, the long form's scratch
     std::vector<mgx_map_counts> h_ms_counts;
     std::vector<uint64_t> h_ms_nodes;
+    // mgx_format_tsv_batch: headers, their offsets, label names (bytes, then the n + 1 begins), line lengths, line_begin (n + 1, then
+    // the capacity counter), the text, the capacity list, the host-formatted lines' (query, length) pairs
+    DevBuf tf_headers, tf_header_offsets, tf_names, tf_len, tf_begin, tf_text, tf_cap, tf_patch;
+    char *h_text = nullptr;                      // the text on the host: pinned memory, grown as needed
+    size_t h_text_bytes = 0;
+    std::vector<uint64_t> h_line_begin;
     mgx_stats hstats;
     hipEvent_t ev[EV_COUNT] = {};
     uint64_t kernels_ran = 0;     // MGX_KERNEL_* bits of the extension kernels the last batch launched
@@ -907,7 +914,8 @@ static int aligner_create(const mgx_graph *g, const mgx_config *config, const mg
                        &A->cursors, &A->d_stats, &A->d_stats_map, &A->scan_tmp, &A->dbg_seeds, &A->seed_hdr, &A->seed_stream, &A->work_key,
                        &A->work_key_sorted, &A->order_in, &A->order, &A->sort_tmp, &A->retry_list, &A->resume_pool[0], &A->resume_pool[1],
                        &A->retry_list2, &A->retry_key[0], &A->retry_key[1], &A->lane_scratch, &A->lane_params, &A->lane_bail, &A->lane_hist, &A->seedlane_scratch, &A->seedlane_params,
-                       &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted })
+                       &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted, &A->tf_headers, &A->tf_header_offsets,
+                       &A->tf_names, &A->tf_len, &A->tf_begin, &A->tf_text, &A->tf_cap, &A->tf_patch })
         b->pooled = true;
     {
         std::string err;
@@ -987,6 +995,7 @@ void mgx_aligner_destroy(mgx_aligner *a) {
     (void)hipSetDevice(a->device);                          // (its own copy: the graph may be gone by now — a binding's GC order)
     (void)hipStreamSynchronize(a->hstream);
     for (auto &e : a->ev) if (e) (void)hipEventDestroy(e);
+    if (a->h_text) (void)hipHostFree(a->h_text);
     if (a->own_stream) (void)hipStreamDestroy(a->hstream);
     delete a;
 }
@@ -1981,26 +1990,24 @@ int mgx_chain_alignments(const mgx_config *config, uint32_t k, const mgx_results
 // mgx_fetch_results / mgx_align_batch (the Python binding and the device-resident batches among them).  What doubling cannot cure stays a capacity status: a query with more
 // alignments than the post_chain_alignments queue holds.  (Label-aware alignment: the retry also doubles the label arenas —
 // alignments per backtracking, aggregator pool, label queues, label sets; derive_limits' label_scale.)
-static int retry_capacity_queries(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, mgx_results *out) {
-    std::vector<uint64_t> todo;
-    // (a query whose post_chain_alignments queue overflowed is flagged by the kernel — RR_CAUSE_QUEUE — and stays a status: no
-    // limit cures it, and six rounds of ever larger arenas would be paid for nothing)
-    for (uint64_t q = 0; q < n; ++q)
-        if (out->status[q] == MGX_ERR_CAPACITY && !(q < A->h_results.size() && A->h_results[q].orientation == RR_CAUSE_QUEUE)) todo.push_back(q);
-    if (todo.empty() || !A->retry_capacity || !d_seqs || !d_offsets) return MGX_OK;
+// The re-alignment itself, for the queries `todo` (ascending) of the batch the device holds: fixed[t] = the results of todo[t]
+// where have[t]; h_off = the batch's offsets, h_seq = its bytes from h_off[todo.front()] on (mgx_format_tsv_batch prints from them).
+static int realign_capacity_queries(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, const std::vector<uint64_t> &todo,
+                                    std::vector<HostResults> &fixed, std::vector<uint8_t> &have, std::vector<uint64_t> &h_off,
+                                    std::vector<char> &h_seq) {
     // the reads in question, from the batch as the device holds it (the caller's buffers, or the upload of a host batch): ONE
     // transfer of the span of the batch between the first and the last of them
-    std::vector<uint64_t> h_off(n + 1);
+    h_off.resize(n + 1);
     HIP_TRY(copy_sync(A, h_off.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
     const uint64_t b0 = h_off[todo.front()], b1 = h_off[todo.back() + 1];
-    std::vector<char> h_seq(b1 - b0 + 1);
+    h_seq.resize(b1 - b0 + 1);
     if (b1 > b0) HIP_TRY(copy_sync(A, h_seq.data(), d_seqs + b0, b1 - b0, hipMemcpyDeviceToHost));
     const char *seqs = h_seq.data();
     auto seq_of = [&](uint64_t q) { return seqs + (h_off[q] - b0); };
     const uint64_t *offsets = h_off.data();
     // results so far, query by query (replaced below)
-    std::vector<HostResults> fixed(todo.size());
-    std::vector<uint8_t> have(todo.size(), 0);
+    fixed.assign(todo.size(), HostResults());
+    have.assign(todo.size(), 0);
     mgx_limits lim;
     mgx_aligner_get_limits(A, &lim);
     mgx_aligner *tmp = nullptr;
@@ -2042,6 +2049,21 @@ static int retry_capacity_queries(mgx_aligner *A, const char *d_seqs, const uint
         pending.swap(again);
         mgx_aligner_get_limits(tmp, &lim);
     }
+    return MGX_OK;
+}
+
+static int retry_capacity_queries(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, mgx_results *out) {
+    std::vector<uint64_t> todo;
+    // (a query whose post_chain_alignments queue overflowed is flagged by the kernel — RR_CAUSE_QUEUE — and stays a status: no
+    // limit cures it, and six rounds of ever larger arenas would be paid for nothing)
+    for (uint64_t q = 0; q < n; ++q)
+        if (out->status[q] == MGX_ERR_CAPACITY && !(q < A->h_results.size() && A->h_results[q].orientation == RR_CAUSE_QUEUE)) todo.push_back(q);
+    if (todo.empty() || !A->retry_capacity || !d_seqs || !d_offsets) return MGX_OK;
+    std::vector<HostResults> fixed;
+    std::vector<uint8_t> have;
+    std::vector<uint64_t> h_off;
+    std::vector<char> h_seq;
+    if (int rc = realign_capacity_queries(A, d_seqs, d_offsets, n, todo, fixed, have, h_off, h_seq)) return rc;
     bool any = false;
     for (uint8_t h : have) any |= h != 0;
     if (!any) return MGX_OK;
@@ -2144,6 +2166,145 @@ size_t mgx_format_tsv_labeled(const mgx_results *res, uint64_t qi, const char *h
         buf[nc] = 0;
     }
     return s.size();
+}
+
+// ---- the TSV text of a batch, written by kernels (tsv_format.hpp, mgx_format.hip) --------------------------
+enum { TF_CNT_SIZE = 0, TF_CNT_WRITE, TF_CNT_HOST_LINES, TF_CNT_D2H_BYTES };
+static std::atomic<uint64_t> g_format_counts[4];        // mgx_format_kernel_launch_counts
+void mgx_format_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_format_counts[x].load(); }
+
+int mgx_format_tsv_batch(mgx_aligner *A, const char *headers, const uint64_t *header_offsets, const char *const *label_names,
+                         uint32_t n_label_names, mgx_text *out) {
+    static_assert(sizeof(TfBatch) == MGX_FORMAT_ARGS_BYTES, "TfBatch differs from what mgx_format.hip takes");
+    if (!A || !out || (n_label_names && !label_names)) return fail(MGX_ERR_INVALID, "null argument");
+    const uint64_t n = A->n_reads;
+    if (n && (!headers || !header_offsets)) return fail(MGX_ERR_INVALID, "null argument");
+    if (A->cfg.post_chain_alignments)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_format_tsv_batch: with post_chain_alignments the chained alignments exist on the host only "
+                                         "(mgx_fetch_results + mgx_format_tsv print them)");
+    A->h_line_begin.assign(n + 1, 0);
+    out->n_queries = n; out->text = A->h_text ? A->h_text : ""; out->line_begin = A->h_line_begin.data();
+    if (!n) return MGX_OK;
+    if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
+    if (!(A->aligned_generation == A->stage_generation && A->last_d_seqs && A->last_d_offsets))
+        return fail(MGX_ERR_INVALID, "mgx_format_tsv_batch: no aligned batch on this handle, or another batch was staged after mgx_align_batch_device");
+    if (n >= 0xFFFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_tsv_batch: more than 2^32 - 2 queries in a batch");
+    HIP_TRY(hipSetDevice(A->graph->device));
+    auto d2h = [&](void *dst, const void *src, size_t bytes) {
+        g_format_counts[TF_CNT_D2H_BYTES] += bytes;
+        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    // inputs of the caller: headers, their offsets, the label names (uploaded with every call: a few hundred bytes)
+    const uint64_t header_bytes = header_offsets[n];
+    std::string name_blob;
+    std::vector<uint32_t> name_begin(1, 0);
+    for (uint32_t j = 0; j < n_label_names; ++j) { name_blob += label_names[j] ? label_names[j] : ""; name_begin.push_back((uint32_t)name_blob.size()); }
+    const size_t names_at = (name_blob.size() + 3) & ~(size_t)3;                 // the begins follow the bytes, 4-byte aligned
+    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
+    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_names.ensure(names_at + name_begin.size() * 4 + 16)) return rc;
+    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
+    if (int rc = A->tf_cap.ensure((n + 1) * 4)) return rc;
+    if (header_bytes) HIP_TRY(hipMemcpyAsync(A->tf_headers.p, headers, header_bytes, hipMemcpyHostToDevice, A->hstream));
+    HIP_TRY(hipMemcpyAsync(A->tf_header_offsets.p, header_offsets, (n + 1) * 8, hipMemcpyHostToDevice, A->hstream));
+    if (n_label_names) {
+        if (!name_blob.empty()) HIP_TRY(hipMemcpyAsync(A->tf_names.p, name_blob.data(), name_blob.size(), hipMemcpyHostToDevice, A->hstream));
+        HIP_TRY(hipMemcpyAsync(A->tf_names.as<char>() + names_at, name_begin.data(), name_begin.size() * 4, hipMemcpyHostToDevice, A->hstream));
+    }
+    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
+    TfBatch b;
+    memset(&b, 0, sizeof(b));
+    b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
+    b.seqs = A->last_d_seqs; b.offsets = A->last_d_offsets;
+    b.headers = A->tf_headers.as<char>(); b.header_offsets = A->tf_header_offsets.as<uint64_t>();
+    b.name_bytes = A->tf_names.as<char>(); b.name_begin = reinterpret_cast<const uint32_t *>(A->tf_names.as<char>() + names_at);
+    b.line_len = d_len; b.line_begin = d_begin;
+    b.cap_list = A->tf_cap.as<uint32_t>(); b.cap_count = reinterpret_cast<unsigned long long *>(d_begin + n + 1);
+    b.n_queries = n; b.n_names = n_label_names; b.min_path_score = A->cfg.min_path_score; b.labeled = A->anno ? 1u : 0u;
+    // pass 1: the line lengths (d_len[n] = 0 closes the scan), the capacity-status queries; the scan gives line_begin
+    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
+    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
+    HIP_TRY((hipError_t)mgx_launch_format_size(&b, A->hstream));
+    ++g_format_counts[TF_CNT_SIZE];
+    auto scan = [&]() -> int {
+        size_t tmp_bytes = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+        if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+        return MGX_OK;
+    };
+    if (int rc = scan()) return rc;
+    uint64_t counters[2] = { 0, 0 };                  // the text's bytes, the capacity-status queries
+    HIP_TRY(d2h(counters, d_begin + n, 16));
+    // the capacity-status queries: aligned again with larger limits, formatted by the host formatter, their lengths patched in
+    std::vector<uint64_t> todo;
+    std::vector<std::string> host_lines;
+    if (counters[1]) {
+        std::vector<uint32_t> cap(counters[1]);
+        HIP_TRY(d2h(cap.data(), A->tf_cap.p, cap.size() * 4));
+        todo.assign(cap.begin(), cap.end());
+        std::sort(todo.begin(), todo.end());
+        if (!A->retry_capacity)
+            return fail(MGX_ERR_CAPACITY, "mgx_format_tsv_batch: query %llu (and %llu more) has a capacity status and retry_capacity is off",
+                        (unsigned long long)todo.front(), (unsigned long long)todo.size() - 1);
+        std::vector<HostResults> fixed;
+        std::vector<uint8_t> have;
+        std::vector<uint64_t> h_off;
+        std::vector<char> h_seq;
+        if (int rc = realign_capacity_queries(A, A->last_d_seqs, A->last_d_offsets, n, todo, fixed, have, h_off, h_seq)) return rc;
+        g_format_counts[TF_CNT_D2H_BYTES] += (n + 1) * 8 + (h_seq.size() - 1);
+        std::vector<const char *> names(label_names, label_names + n_label_names);
+        for (auto &nm : names) if (!nm) nm = "";
+        std::vector<uint64_t> patch_len(todo.size());
+        host_lines.resize(todo.size());
+        for (size_t t = 0; t < todo.size(); ++t) {
+            const uint64_t q = todo[t];
+            if (!have[t])
+                return fail(MGX_ERR_CAPACITY, "mgx_format_tsv_batch: query %llu keeps its capacity status after the retry", (unsigned long long)q);
+            mgx_results v;
+            fixed[t].view(&v);
+            const std::string header(headers + header_offsets[q], headers + header_offsets[q + 1]);
+            const char *query = h_seq.data() + (h_off[q] - h_off[todo.front()]);
+            const size_t qlen = h_off[q + 1] - h_off[q];
+            std::string &line = host_lines[t];
+            line.resize(mgx_format_tsv_labeled(&v, 0, header.c_str(), query, qlen, A->cfg.min_path_score, names.data(), n_label_names, nullptr, 0) + 1);
+            mgx_format_tsv_labeled(&v, 0, header.c_str(), query, qlen, A->cfg.min_path_score, names.data(), n_label_names, &line[0], line.size());
+            line.pop_back();                         // (the formatter's NUL)
+            patch_len[t] = line.size();
+        }
+        A->hstats.n_capacity_retried = todo.size();
+        g_format_counts[TF_CNT_HOST_LINES] += todo.size();
+        // (query, length) pairs: the queries as 4-byte words behind the 8-byte lengths
+        if (int rc = A->tf_patch.ensure(todo.size() * 12 + 16)) return rc;
+        for (size_t t = 0; t < todo.size(); ++t) cap[t] = (uint32_t)todo[t];
+        uint32_t *d_pq = reinterpret_cast<uint32_t *>(A->tf_patch.as<uint64_t>() + todo.size());
+        HIP_TRY(hipMemcpyAsync(A->tf_patch.p, patch_len.data(), todo.size() * 8, hipMemcpyHostToDevice, A->hstream));
+        HIP_TRY(hipMemcpyAsync(d_pq, cap.data(), todo.size() * 4, hipMemcpyHostToDevice, A->hstream));
+        HIP_TRY((hipError_t)mgx_launch_format_patch(d_len, d_pq, A->tf_patch.as<uint64_t>(), (uint32_t)todo.size(), A->hstream));
+        if (int rc = scan()) return rc;
+        HIP_TRY(d2h(counters, d_begin + n, 8));
+        HIP_TRY(hipStreamSynchronize(A->hstream));   // (patch_len and cap are read by the copies above)
+    }
+    // pass 2: the text
+    const uint64_t text_bytes = counters[0];
+    if (int rc = A->tf_text.ensure(text_bytes + 16)) return rc;
+    if (text_bytes + 1 > A->h_text_bytes) {
+        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
+        const size_t want = text_bytes + text_bytes / 8 + 4096;
+        void *p = nullptr;
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(MGX_ERR_OOM, "hipHostMalloc(%zu) failed", want); }
+        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
+    }
+    b.text = A->tf_text.as<char>();
+    HIP_TRY((hipError_t)mgx_launch_format_write(&b, A->hstream));
+    ++g_format_counts[TF_CNT_WRITE];
+    g_format_counts[TF_CNT_D2H_BYTES] += text_bytes;
+    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
+    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
+    for (size_t t = 0; t < todo.size(); ++t) memcpy(A->h_text + A->h_line_begin[todo[t]], host_lines[t].data(), host_lines[t].size());
+    out->text = A->h_text;
+    return MGX_OK;
 }
 
 // ---- metagraph align --json (cli/align.cpp:287-305): Alignment::to_json (alignment.cpp:883-963) + path_json (:704-881),

@@ -298,6 +298,25 @@ class HipDBGAligner : public IDBGAligner {
         if (int rc = mgx_align_batch_device(a_, blob.data(), offsets.data(), seq_batch.size(), 0))
             throw std::runtime_error(std::string("mgx_align_batch_device: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
     }
+    // The TSV text of the batch align_batch_device ran last, written on the device (mgx_format_tsv_batch): what format_alignment
+    // gives for every query, in query order.  label_names: as for format_alignment (null: labels print as numbers).  The view
+    // is the handle's and stays valid until its next batch.  Throws for post_chain_alignments (the chained alignments exist
+    // on the host only: align_batch with a callback remains the path) and for capacity statuses no retry cures.
+    std::string_view format_batch_tsv(const std::vector<Query> &seq_batch, const std::vector<std::string> *label_names = nullptr) const {
+        std::string headers;
+        std::vector<uint64_t> offsets(seq_batch.size() + 1, 0);
+        for (size_t t = 0; t < seq_batch.size(); ++t) {
+            headers += seq_batch[t].first;
+            offsets[t + 1] = headers.size();
+        }
+        std::vector<const char *> names;
+        if (label_names) for (const std::string &nm : *label_names) names.push_back(nm.c_str());
+        mgx_text text{};
+        if (int rc = mgx_format_tsv_batch(a_, headers.data(), offsets.data(), names.empty() ? nullptr : names.data(), (uint32_t)names.size(), &text))
+            throw std::runtime_error(std::string("mgx_format_tsv_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        if (text.n_queries != seq_batch.size()) throw std::runtime_error("mgx_format_tsv_batch: the handle's batch is not this one");
+        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+    }
     mgx_aligner *handle() const { return a_; }
     static void deliver(const mgx_results &res, const std::vector<Query> &seq_batch, const AlignmentCallback &callback) {
         std::vector<AlignmentResults> results;

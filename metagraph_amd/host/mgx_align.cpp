@@ -10,6 +10,8 @@
 //                             --align-length N (windows of N < k characters; 0 = k, above k: a warning and k);
 //                             --fwd-and-reverse (every record followed by its reverse complement under the same name).
 //                             Output in input order; no annotation is loaded in this mode
+//             [--format-on-device]  the TSV text of every batch is written by kernels (mgx_format_tsv_batch) and printed with one write
+//                             per batch, instead of one host-built string per query; same bytes.  Not with --map or --rccl-gather
 //             [--devices D]   in-process multi-GPU: one graph replica per device, whole batches routed round-robin, no collective
 //             [--rccl-gather] with --devices D: one worker per device, batches in rounds of D; every round's device results are
 //                             gathered to device 0 over RCCL (mgx_gather_*: the C-ABI of north_star's "RCCL-over-xGMI only to
@@ -105,7 +107,7 @@ int main(int argc, char **argv) {
     mgx_limits lim;
     bool have_lim = false;
     int devices = 1;
-    bool rccl_gather = false;
+    bool rccl_gather = false, format_on_device = false;
     std::vector<const char *> anno_paths;
     std::vector<std::string> kernel_options;            // --kernel-option key=value: result-preserving kernel selection (A/B runs)
     bool map_mode = false, count_kmers = false, query_presence = false, filter_present = false, fwd_and_reverse = false;
@@ -130,9 +132,14 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-a") && i + 1 < argc) anno_paths.push_back(argv[++i]);
         else if (!strcmp(argv[i], "--kernel-option") && i + 1 < argc) kernel_options.push_back(argv[++i]);
         else if (!strcmp(argv[i], "--rccl-gather")) rccl_gather = true;
+        else if (!strcmp(argv[i], "--format-on-device")) format_on_device = true;
         else if (!strcmp(argv[i], "--time")) report_time = true;            // wall time of the align loop (batches -> results printed) on stderr
         else if (!strcmp(argv[i], "--canonical")) graph_mode = MGX_MODE_CANONICAL;
         else if (!strcmp(argv[i], "--primary")) graph_mode = MGX_MODE_PRIMARY;         // aligned through the CanonicalDBG wrapper
+    }
+    if (format_on_device && (map_mode || rccl_gather)) {
+        fprintf(stderr, "error: --format-on-device formats the alignment TSV of a batch on its own device: not with %s\n", map_mode ? "--map" : "--rccl-gather");
+        return 1;
     }
     if (map_mode) anno_paths.clear();                    // no annotation is loaded in this mode (cli/align.cpp:316-318)
     try {
@@ -252,6 +259,13 @@ int main(int argc, char **argv) {
                     // (the workers of one device share it: every handle on its own stream, its arenas sized for its share)
                     aligner.set_device_share((threads + (unsigned)devices - 1) / (unsigned)devices);
                     for (const std::string &opt : kernel_options) aligner.set_kernel_option(opt);
+                    if (format_on_device) {
+                        aligner.align_batch_device(batches[bi]);
+                        const std::string_view text = aligner.format_batch_tsv(batches[bi], annotation ? &label_names : nullptr);
+                        std::lock_guard<std::mutex> lock(print_mutex);
+                        std::cout.write(text.data(), (std::streamsize)text.size());
+                        continue;
+                    }
                     aligner.align_batch(batches[bi], [&](const std::string &header, AlignmentResults &&paths) {
                         const std::string res = format_alignment(header, paths, cfg.min_path_score, annotation ? &label_names : nullptr);
                         std::lock_guard<std::mutex> lock(print_mutex);
