@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_format_tsv_batch / mgx_format_kernel_launch_counts (the TSV text of a batch, written
+#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_read_parser_* / mgx_parse_reads / mgx_parse_kernel_launch_counts (FASTA / FASTQ text to
+                                * read batches on the device); before that mgx_format_tsv_batch / mgx_format_kernel_launch_counts (the TSV text of a batch, written
                                 * by kernels); before that mgx_map_summary_batch / mgx_map_present / mgx_format_map / mgx_map_kernel_launch_counts
                                 * (`align --map`: per-read k-mer counts, presence, --align-length < k);
                                 * 6 (round 6, late): mgx_gather_* (RCCL gather of the device results); 5 (round 6): mgx_stats::n_seed_lane_reads / seed_lane_ms / seed_lane_left_reads, streams, coordinates,
@@ -562,6 +563,65 @@ int mgx_format_tsv_batch(mgx_aligner *a, const char *headers, const uint64_t *he
 /* Test hook: out4 = launches of the size kernel, launches of the write kernel, queries whose line was formatted on the host
  * (capacity retries), bytes copied device-to-host by mgx_format_tsv_batch — since the library was loaded. */
 void mgx_format_kernel_launch_counts(uint64_t *out4);
+
+/* ---- FASTA / FASTQ text to read batches, parsed on the device --------------------------------------------
+ * mgx_parse_reads turns the bytes of a FASTA / FASTQ file (plain text: gzip stays with the caller) into the arrays the calls
+ * above take, without a per-record step on the host: `seqs` / `offsets` in DEVICE memory are the arguments of
+ * mgx_align_batch_device(..., seqs_on_device = 1); `names` / `name_offsets` in HOST memory are the arguments of
+ * mgx_format_tsv_batch; `host_offsets` is a host copy of `offsets` (batching by bases, cli/align.cpp:429-438).  The sequences
+ * themselves do not travel back (mgx_read_parser_fetch copies them for who wants them).
+ *
+ * Grammar: kseq's kseq_read restricted to files where it is unambiguous; anything outside it is MGX_ERR_INVALID — never parsed
+ * differently — with the byte position of the offending line in mgx_last_error(), and `out` untouched.
+ *   - format: the first byte of the chunk's first non-empty line: '>' FASTA, '@' FASTQ (flags = MGX_READS_FASTA / MGX_READS_FASTQ
+ *     forces one; a caller that feeds chunks passes the first chunk's out->format for the later ones).
+ *   - name: the bytes behind the marker up to the first isspace() byte or the end of the line; the comment is dropped; empty
+ *     names are kept.  A line excludes its '\n' and a '\r' directly in front of it.
+ *   - FASTA: every line up to the next header line is a sequence line, copied verbatim; empty lines add nothing; a sequence line
+ *     that begins with '@' or '+' is refused.
+ *   - FASTQ: records are strictly four lines counted from the start of the chunk, empty lines count: line 0 begins with '@', line 2
+ *     with '+', line 1 with none of "@+>", lines 1 and 3 have the same length (multi-line FASTQ is refused).  Empty lines behind
+ *     the last record are ignored.
+ *   - final == 0: only complete records are consumed (FASTQ: four lines, the fourth ended by '\n'; FASTA: another header line
+ *     follows); out->consumed = their bytes, where the caller's next chunk starts; n_records == 0 with MGX_OK asks for a longer
+ *     chunk.  final != 0: an unterminated last line ends at the end of the buffer and consumed = n_bytes.
+ *   - chunks of 2^32 - 1 bytes or more: MGX_ERR_INVALID.  Offsets are 64-bit.
+ * The views are owned by the handle: valid until its next parse or its destruction; the device arrays must not be in use by
+ * another stream's work when the next parse starts (mgx_fetch_results / mgx_format_tsv_batch have synchronised by then).
+ * A parse that fails or is refused ends the previous parse's views all the same (their buffers may have been reused): the handle
+ * then holds no records, mgx_read_parser_slice accepts only the empty range and mgx_read_parser_fetch copies nothing.
+ * text_on_device != 0: the text is read by kernels on the parser's own non-blocking stream, which waits for no other stream —
+ * the work that produces the text must have completed (a stream or device synchronise by the caller) before the call.
+ * `seqs` has 16 bytes of room behind the last sequence, like the staged copy of host reads.
+ * A sub-batch (records first .. first + n): mgx_read_parser_slice returns the device pointers to pass on — offsets that start at
+ * 0, as the aligner's kernels expect; valid until the next slice or parse.  Names of a sub-batch: names + name_offsets[first]
+ * with the offsets rebased by the caller. */
+#define MGX_READS_FASTA 1u
+#define MGX_READS_FASTQ 2u
+typedef struct mgx_read_parser mgx_read_parser;
+typedef struct mgx_reads {
+    uint64_t n_records, consumed;
+    uint32_t format;                /* MGX_READS_FASTA / MGX_READS_FASTQ; 0: no non-empty line seen */
+    const char *seqs;               /* DEVICE */
+    const uint64_t *offsets;        /* DEVICE, n_records + 1 */
+    const uint64_t *host_offsets;   /* HOST copy of offsets */
+    const char *names;              /* HOST */
+    const uint64_t *name_offsets;   /* HOST, n_records + 1 */
+} mgx_reads;
+int mgx_read_parser_create(int device, mgx_read_parser **out);
+void mgx_read_parser_destroy(mgx_read_parser *p);
+int mgx_parse_reads(mgx_read_parser *p, const char *text, uint64_t n_bytes, int text_on_device, int final, uint32_t flags,
+                    mgx_reads *out);
+int mgx_read_parser_slice(mgx_read_parser *p, uint64_t first, uint64_t n, const char **seqs, const uint64_t **offsets);
+/* device -> host copy of the last parse: seqs_out takes host_offsets[n_records] bytes, offsets_out n_records + 1 entries */
+int mgx_read_parser_fetch(mgx_read_parser *p, char *seqs_out, uint64_t *offsets_out);
+/* Test hook: out4 = launches of the line-pass kernels, launches of the copy-pass kernels, bytes copied host-to-device, bytes
+ * copied device-to-host by the parser — since the library was loaded. */
+void mgx_parse_kernel_launch_counts(uint64_t *out4);
+/* Page-locked host memory for the text handed to mgx_parse_reads (a copy from pageable memory is staged by the runtime and runs at
+ * a fraction of the link's rate).  NULL on failure (mgx_last_error). */
+void *mgx_pinned_alloc(size_t bytes);
+void mgx_pinned_free(void *p);
 
 /* mgx_results_from_raw for the records of a label-aware aligner (labeled != 0: every alignment's arrays are followed by
  * its label list in the stream). */

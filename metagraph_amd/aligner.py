@@ -212,6 +212,12 @@ class Aligner:
         """Reads already in HBM (device pointers); results stay on the device until fetch()."""
         _check(capi.lib().mgx_align_batch_device(self.h, seqs_ptr, offsets_ptr, n, 1))
 
+    def align_batch_device(self, reads, first=0, n=None):
+        """The records first .. first + n of a ParsedReads (ReadParser.parse) from the parser's device arrays; results stay on
+        the device until fetch() / format_tsv_batch(reads.names_of(first, n))."""
+        seqs, offsets, n = reads.device_slice(first, n)
+        _check(capi.lib().mgx_align_batch_device(self.h, seqs, offsets, n, 1))
+
     def fetch(self):
         res = capi.Results()
         _check(capi.lib().mgx_fetch_results(self.h, C.byref(res)))
@@ -286,18 +292,98 @@ class Aligner:
         """mgx_format_tsv_batch: the TSV text of the batch align_device / align_batch ran last, written by kernels.
         headers: one str / bytes per query; label_names: names of labels 0 .. len - 1 (label-aware aligners; others print as
         numbers).  -> (bytes of all lines in query order, numpy uint64 array of len(headers) + 1 line offsets)."""
-        hs = [h if isinstance(h, bytes) else h.encode("latin-1") for h in headers]
-        hoff = np.zeros(len(hs) + 1, dtype=np.uint64)
-        if hs:
-            hoff[1:] = np.cumsum([len(h) for h in hs])
+        if isinstance(headers, tuple) and len(headers) == 2 and isinstance(headers[1], np.ndarray):
+            blob, hoff = headers                   # the flat arrays of ParsedReads.names_of: bytes, uint64 offsets from 0
+            n_headers = len(hoff) - 1
+        else:
+            hs = [h if isinstance(h, bytes) else h.encode("latin-1") for h in headers]
+            hoff = np.zeros(len(hs) + 1, dtype=np.uint64)
+            if hs:
+                hoff[1:] = np.cumsum([len(h) for h in hs])
+            blob, n_headers = b"".join(hs), len(hs)
         names = [n if isinstance(n, bytes) else n.encode() for n in (label_names or [])]
         arr = (C.c_char_p * len(names))(*names) if names else None
         t = capi.Text()
-        _check(capi.lib().mgx_format_tsv_batch(self.h, b"".join(hs), hoff.ctypes.data, arr, len(names), C.byref(t)))
-        if t.n_queries != len(hs):
-            raise ValueError("format_tsv_batch: %d headers for a batch of %d queries" % (len(hs), t.n_queries))
-        lb = np.ctypeslib.as_array(t.line_begin, shape=(len(hs) + 1,)).copy()
+        _check(capi.lib().mgx_format_tsv_batch(self.h, blob, hoff.ctypes.data, arr, len(names), C.byref(t)))
+        if t.n_queries != n_headers:
+            raise ValueError("format_tsv_batch: %d headers for a batch of %d queries" % (n_headers, t.n_queries))
+        lb = np.ctypeslib.as_array(t.line_begin, shape=(n_headers + 1,)).copy()
         return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+
+
+class ParsedReads:
+    """What ReadParser.parse returns: a view of the parser's arrays, valid until its next parse.  n_records, consumed, format;
+    seqs / offsets: device pointers (ints); host_offsets, name_offsets: numpy uint64 copies; names: bytes (all names, end to end)."""
+
+    def __init__(self, parser, r):
+        self.parser = parser
+        self.n_records, self.consumed, self.format = int(r.n_records), int(r.consumed), int(r.format)
+        self.seqs, self.offsets = r.seqs, r.offsets
+        n = self.n_records
+        self.host_offsets = np.ctypeslib.as_array(r.host_offsets, shape=(n + 1,)).copy()
+        self.name_offsets = np.ctypeslib.as_array(r.name_offsets, shape=(n + 1,)).copy()
+        self.names = C.string_at(r.names, int(self.name_offsets[n])) if int(self.name_offsets[n]) else b""
+
+    def name_list(self):
+        o = self.name_offsets
+        return [self.names[int(o[r]):int(o[r + 1])] for r in range(self.n_records)]
+
+    def names_of(self, first=0, n=None):
+        """the names of records first .. first + n as (bytes, offsets from 0): the headers of Aligner.format_tsv_batch"""
+        n = self.n_records - first if n is None else n
+        o = self.name_offsets[first:first + n + 1]
+        return self.names[int(o[0]):int(o[-1])], np.ascontiguousarray(o - o[0])
+
+    def device_slice(self, first=0, n=None):
+        """-> (seqs, offsets, n): device pointers of the sub-batch, offsets from 0 (mgx_read_parser_slice)"""
+        n = self.n_records - first if n is None else n
+        seqs, offsets = C.c_void_p(), C.c_void_p()
+        _check(capi.lib().mgx_read_parser_slice(self.parser.h, first, n, C.byref(seqs), C.byref(offsets)))
+        return seqs, offsets, n
+
+    def to_host(self):
+        """-> (seqs bytes, offsets numpy uint64): the sequences copied back (mgx_read_parser_fetch)"""
+        total = int(self.host_offsets[-1])
+        buf = C.create_string_buffer(max(1, total))
+        offs = np.zeros(self.n_records + 1, dtype=np.uint64)
+        _check(capi.lib().mgx_read_parser_fetch(self.parser.h, buf, offs.ctypes.data))
+        return buf.raw[:total], offs
+
+
+class ReadParser:
+    """mgx_read_parser: FASTA / FASTQ text to read batches on the device, no per-record work on the host."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _check(capi.lib().mgx_read_parser_create(device, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and capi is not None:
+            capi.lib().mgx_read_parser_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def parse(self, data, final=True, text_on_device=False, flags=0, n_bytes=None):
+        """data: bytes-like host text, or with text_on_device a device pointer (int) and n_bytes.  final=False: only complete
+        records are consumed (ParsedReads.consumed says where the next chunk starts; pass the first chunk's format as flags).
+        Outside the grammar: MgxError(MGX_ERR_INVALID) naming the byte position."""
+        r = capi.Reads()
+        if text_on_device:
+            ptr, n = data, n_bytes
+        else:
+            keep = np.frombuffer(data, dtype=np.uint8)
+            ptr, n = (keep.ctypes.data if len(keep) else None), len(keep)
+        _check(capi.lib().mgx_parse_reads(self.h, ptr, n, int(bool(text_on_device)), int(bool(final)), flags, C.byref(r)))
+        return ParsedReads(self, r)
+
+
+def parse_kernel_launch_counts():
+    """mgx_parse_kernel_launch_counts -> (line-pass kernel launches, copy-pass kernel launches, bytes host-to-device, bytes
+    device-to-host) since the library was loaded"""
+    out = (C.c_uint64 * 4)()
+    capi.lib().mgx_parse_kernel_launch_counts(out)
+    return tuple(int(x) for x in out)
 
 
 def format_kernel_launch_counts():

@@ -85,6 +85,14 @@ class Text(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("text", C.c_void_p), ("line_begin", C.POINTER(C.c_uint64))]
 
 
+class Reads(C.Structure):
+    """mgx_reads: what mgx_parse_reads leaves (seqs / offsets: device pointers; the rest: host)"""
+    _fields_ = [("n_records", C.c_uint64), ("consumed", C.c_uint64), ("format", C.c_uint32), ("seqs", C.c_void_p),
+                ("offsets", C.c_void_p), ("host_offsets", C.POINTER(C.c_uint64)), ("names", C.c_void_p),
+                ("name_offsets", C.POINTER(C.c_uint64))]
+
+
+MGX_READS_FASTA, MGX_READS_FASTQ = 1, 2
 MGX_MAP_WANT_NODES = 1
 MGX_MAP_FMT_NODES, MGX_MAP_FMT_COUNT_KMERS, MGX_MAP_FMT_QUERY_PRESENCE, MGX_MAP_FMT_FILTER_PRESENT = 0, 1, 2, 3
 
@@ -288,6 +296,18 @@ def lib():
     L.mgx_format_tsv_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Text)]
     L.mgx_format_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.mgx_format_kernel_launch_counts.restype = None
+    L.mgx_read_parser_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mgx_read_parser_destroy.argtypes = [C.c_void_p]
+    L.mgx_read_parser_destroy.restype = None
+    L.mgx_parse_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.POINTER(Reads)]
+    L.mgx_read_parser_slice.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mgx_read_parser_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mgx_parse_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_parse_kernel_launch_counts.restype = None
+    L.mgx_pinned_alloc.argtypes = [C.c_size_t]
+    L.mgx_pinned_alloc.restype = C.c_void_p
+    L.mgx_pinned_free.argtypes = [C.c_void_p]
+    L.mgx_pinned_free.restype = None
     L.mgx_aligner_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.mgx_config_init_default.argtypes = [C.POINTER(Config)]
     L.mgx_config_init_cli.argtypes = [C.POINTER(Config), C.c_uint32]

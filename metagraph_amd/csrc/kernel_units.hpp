@@ -14,6 +14,7 @@ constexpr size_t MGX_LANE_PARAMS_BYTES = 848;           // sizeof(LaneParams), l
 constexpr size_t MGX_SEED_LANE_PARAMS_BYTES = 824;      // sizeof(SeedLaneParams), seed_lane.hpp
 constexpr size_t MGX_DEV_GRAPH_BYTES = 160;             // sizeof(DevGraph), dev_graph.hpp
 constexpr size_t MGX_FORMAT_ARGS_BYTES = 128;           // sizeof(TfBatch), tsv_format.hpp
+constexpr size_t MGX_PARSE_ARGS_BYTES = 144;            // sizeof(RpChunk), reads_parse.hpp
 
 struct mgx_annotation;
 
@@ -76,6 +77,15 @@ uint32_t mgx_map_summary_short_max(void);
 int mgx_launch_format_size(const void *args, void *stream);
 int mgx_launch_format_write(const void *args, void *stream);
 int mgx_launch_format_patch(uint64_t *line_len, const uint32_t *queries, const uint64_t *lens, uint32_t m, void *stream);
+
+// mgx_parse.hip: FASTA / FASTQ text to read batches (reads_parse.hpp).  args: an RpChunk (host memory).  count: the '\n' mask and
+// count of every 64-byte span; table: line_begin[] from the masks and the scanned counts; classify: what every line adds (items);
+// records: offsets[] / name_offsets[] and the counters from the scanned items; copy: the sequence bytes, or (names != 0) the names.
+int mgx_launch_parse_count(const void *args, void *stream);
+int mgx_launch_parse_table(const void *args, void *stream);
+int mgx_launch_parse_classify(const void *args, void *stream);
+int mgx_launch_parse_records(const void *args, void *stream);
+int mgx_launch_parse_copy(const void *args, int names, void *stream);
 
 // mgx_annot.hip: the matrix as the label-aware extension kernels read it (AlignParams::anno_*), and the annotation's
 // process-unique id

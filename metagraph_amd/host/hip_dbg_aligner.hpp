@@ -234,6 +234,39 @@ class HipAnnotation {
     mgx_annotation *a_ = nullptr;
 };
 
+// FASTA / FASTQ text to read batches on the device (mgx_read_parser: csrc/reads_parse.hpp).  parse() returns the handle's view:
+// seqs / offsets in device memory, names / name_offsets / host_offsets on the host; valid until the next parse.  A file outside
+// the grammar throws ParseRefused with the message of the C-ABI (it names the byte position).
+struct ParseRefused : std::runtime_error { using std::runtime_error::runtime_error; };
+class HipReadParser {
+  public:
+    explicit HipReadParser(int device = 0) {
+        if (int rc = mgx_read_parser_create(device, &p_))
+            throw std::runtime_error(std::string("mgx_read_parser_create: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+    }
+    ~HipReadParser() { mgx_read_parser_destroy(p_); }
+    HipReadParser(const HipReadParser &) = delete;
+    HipReadParser &operator=(const HipReadParser &) = delete;
+    // flags: 0, or the format of the file's first chunk for the later ones (mgx_reads::format)
+    mgx_reads parse(const char *text, uint64_t n_bytes, bool final_chunk, uint32_t flags = 0, bool text_on_device = false) {
+        mgx_reads r{};
+        if (int rc = mgx_parse_reads(p_, text, n_bytes, text_on_device ? 1 : 0, final_chunk ? 1 : 0, flags, &r)) {
+            if (rc == MGX_ERR_INVALID) throw ParseRefused(mgx_last_error());
+            throw std::runtime_error(std::string("mgx_parse_reads: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        }
+        return r;
+    }
+    // device pointers of records first .. first + n, offsets from 0; valid until the next slice or parse
+    void slice(uint64_t first, uint64_t n, const char **seqs, const uint64_t **offsets) {
+        if (int rc = mgx_read_parser_slice(p_, first, n, seqs, offsets))
+            throw std::runtime_error(std::string("mgx_read_parser_slice: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+    }
+    mgx_read_parser *handle() const { return p_; }
+
+  private:
+    mgx_read_parser *p_ = nullptr;
+};
+
 class HipDBGAligner : public IDBGAligner {
   public:
     // throws std::runtime_error like the reference when check_config_scores() fails (dbg_aligner.cpp:55-56)
@@ -315,6 +348,23 @@ class HipDBGAligner : public IDBGAligner {
         if (int rc = mgx_format_tsv_batch(a_, headers.data(), offsets.data(), names.empty() ? nullptr : names.data(), (uint32_t)names.size(), &text))
             throw std::runtime_error(std::string("mgx_format_tsv_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
         if (text.n_queries != seq_batch.size()) throw std::runtime_error("mgx_format_tsv_batch: the handle's batch is not this one");
+        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+    }
+    // ... over reads that are in device memory already (HipReadParser::slice): n reads, offsets from 0
+    void align_batch_device(const char *d_seqs, const uint64_t *d_offsets, uint64_t n) const {
+        if (int rc = mgx_align_batch_device(a_, d_seqs, d_offsets, n, 1))
+            throw std::runtime_error(std::string("mgx_align_batch_device: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+    }
+    // ... with the names as flat arrays (mgx_reads::names / name_offsets; `name_offsets` points at the batch's first record: n + 1 entries)
+    std::string_view format_batch_tsv(const char *names, const uint64_t *name_offsets, uint64_t n, const std::vector<std::string> *label_names = nullptr) const {
+        std::vector<uint64_t> offsets(n + 1);
+        for (uint64_t t = 0; t <= n; ++t) offsets[t] = name_offsets[t] - name_offsets[0];
+        std::vector<const char *> lnames;
+        if (label_names) for (const std::string &nm : *label_names) lnames.push_back(nm.c_str());
+        mgx_text text{};
+        if (int rc = mgx_format_tsv_batch(a_, names + name_offsets[0], offsets.data(), lnames.empty() ? nullptr : lnames.data(), (uint32_t)lnames.size(), &text))
+            throw std::runtime_error(std::string("mgx_format_tsv_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        if (text.n_queries != n) throw std::runtime_error("mgx_format_tsv_batch: the handle's batch is not this one");
         return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
     }
     mgx_aligner *handle() const { return a_; }

@@ -12,6 +12,13 @@
 //                             Output in input order; no annotation is loaded in this mode
 //             [--format-on-device]  the TSV text of every batch is written by kernels (mgx_format_tsv_batch) and printed with one write
 //                             per batch, instead of one host-built string per query; same bytes.  Not with --map or --rccl-gather
+//             [--parse-on-device]  with --format-on-device, -p 1 and --devices 1: the file is read in large chunks with read(2) into
+//                             a pinned buffer and parsed by kernels (mgx_parse_reads) — file bytes in, TSV bytes out, no per-read
+//                             host work.  Files inside the parser's grammar print the same bytes, with two exceptions
+//                             where the parser follows kseq and read_records does not: a record with an empty name is printed
+//                             (read_records drops it), and in a CRLF file the '\r' is not part of the sequence (std::getline
+//                             keeps it).  Files outside the grammar: exit status 1 and the byte position.  Not with --map or
+//                             --rccl-gather
 //             [--devices D]   in-process multi-GPU: one graph replica per device, whole batches routed round-robin, no collective
 //             [--rccl-gather] with --devices D: one worker per device, batches in rounds of D; every round's device results are
 //                             gathered to device 0 over RCCL (mgx_gather_*: the C-ABI of north_star's "RCCL-over-xGMI only to
@@ -31,6 +38,9 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+
+#include <fcntl.h>
+#include <unistd.h>
 
 #include "hip_dbg_aligner.hpp"
 
@@ -107,7 +117,8 @@ int main(int argc, char **argv) {
     mgx_limits lim;
     bool have_lim = false;
     int devices = 1;
-    bool rccl_gather = false, format_on_device = false;
+    bool rccl_gather = false, format_on_device = false, parse_on_device = false;
+    uint64_t parse_chunk_bytes = 256ull << 20;         // --parse-chunk-bytes N (test hook: several chunks from a small file)
     std::vector<const char *> anno_paths;
     std::vector<std::string> kernel_options;            // --kernel-option key=value: result-preserving kernel selection (A/B runs)
     bool map_mode = false, count_kmers = false, query_presence = false, filter_present = false, fwd_and_reverse = false;
@@ -133,9 +144,17 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--kernel-option") && i + 1 < argc) kernel_options.push_back(argv[++i]);
         else if (!strcmp(argv[i], "--rccl-gather")) rccl_gather = true;
         else if (!strcmp(argv[i], "--format-on-device")) format_on_device = true;
+        else if (!strcmp(argv[i], "--parse-on-device")) parse_on_device = true;
+        else if (!strcmp(argv[i], "--parse-chunk-bytes") && i + 1 < argc) parse_chunk_bytes = std::max<uint64_t>(1, strtoull(argv[++i], nullptr, 10));
         else if (!strcmp(argv[i], "--time")) report_time = true;            // wall time of the align loop (batches -> results printed) on stderr
         else if (!strcmp(argv[i], "--canonical")) graph_mode = MGX_MODE_CANONICAL;
         else if (!strcmp(argv[i], "--primary")) graph_mode = MGX_MODE_PRIMARY;         // aligned through the CanonicalDBG wrapper
+    }
+    if (parse_on_device && (map_mode || rccl_gather || !format_on_device || threads != 1 || devices != 1)) {
+        fprintf(stderr, "error: --parse-on-device hands the parser's device arrays to one aligner and its formatter: %s\n",
+                map_mode ? "not with --map" : rccl_gather ? "not with --rccl-gather" : !format_on_device ? "it needs --format-on-device"
+                : "with -p 1 and --devices 1 only");
+        return 1;
     }
     if (format_on_device && (map_mode || rccl_gather)) {
         fprintf(stderr, "error: --format-on-device formats the alignment TSV of a batch on its own device: not with %s\n", map_mode ? "--map" : "--rccl-gather");
@@ -188,6 +207,81 @@ int main(int argc, char **argv) {
             annotation = std::make_unique<HipAnnotation>(n_rows, col_begin, rows, 0);
         }
         if ((unsigned)devices > threads) threads = (unsigned)devices;                  // at least one worker per device
+        if (parse_on_device) {
+            // file bytes in, TSV bytes out: read(2) into a pinned buffer, a parse per chunk (the unconsumed tail is carried over to
+            // the next chunk), batches cut at the reference's rule from the parser's host copy of the offsets, aligned from
+            // its device arrays, printed from the formatter's text
+            const int fd = open(argv[2], O_RDONLY);
+            if (fd < 0) { fprintf(stderr, "cannot open %s\n", argv[2]); return 1; }
+            struct Pinned {
+                char *p = nullptr; size_t cap = 0;
+                ~Pinned() { mgx_pinned_free(p); }
+                void grow(size_t want, size_t keep) {
+                    if (want <= cap) return;
+                    void *q = mgx_pinned_alloc(want);
+                    if (!q) throw std::runtime_error(std::string("the read buffer: ") + mgx_last_error());
+                    if (keep) memcpy(q, p, keep);
+                    mgx_pinned_free(p);
+                    p = static_cast<char *>(q); cap = want;
+                }
+            } buf;
+            parse_chunk_bytes = std::min<uint64_t>(parse_chunk_bytes, 0xF0000000ull);
+            const HipBOSSGraph &graph = graphs.for_worker(0);
+            HipReadParser parser(0);
+            const auto t0 = std::chrono::steady_clock::now();
+            size_t have = 0, n_queries = 0, n_batches = 0;
+            uint64_t file_at = 0;                      // the file position of buf[0]
+            uint32_t format = 0;
+            bool eof = false;
+            int status = 0;
+            while (!eof || have) {
+                // fill: one more chunk behind what the last parse left
+                buf.grow(have + parse_chunk_bytes, have);
+                while (!eof && have < buf.cap) {
+                    const ssize_t got = read(fd, buf.p + have, std::min<size_t>(buf.cap - have, parse_chunk_bytes));
+                    if (got < 0) { fprintf(stderr, "error: reading %s failed\n", argv[2]); close(fd); return 1; }
+                    if (got == 0) eof = true; else have += (size_t)got;
+                    if (have >= parse_chunk_bytes) break;
+                }
+                if (have >= 0xFFFFFFF0ull) { fprintf(stderr, "error: a record of %s does not fit a chunk of 4 GB; run without --parse-on-device\n", argv[2]); status = 1; break; }
+                mgx_reads r;
+                try { r = parser.parse(buf.p, have, eof, format); }
+                catch (const ParseRefused &e) {
+                    fprintf(stderr, "error: %s: %s (positions count from byte %llu of the file); run without --parse-on-device\n", argv[2], e.what(), (unsigned long long)file_at);
+                    status = 1;
+                    break;
+                }
+                if (!format) format = r.format;
+                for (uint64_t i = 0; i < r.n_records;) {
+                    // align.cpp:431-442: a record is added while the running total is <= batch_size
+                    const uint64_t first = i;
+                    while (i < r.n_records && r.host_offsets[i] - r.host_offsets[first] <= batch_size) ++i;
+                    const char *d_seqs; const uint64_t *d_offsets;
+                    parser.slice(first, i - first, &d_seqs, &d_offsets);
+                    std::unique_ptr<HipDBGAligner> aligner_p(annotation
+                        ? new HipDBGAligner(graph, cfg, *annotation, have_lim ? &lim : nullptr)
+                        : new HipDBGAligner(graph, cfg, have_lim ? &lim : nullptr));
+                    for (const std::string &opt : kernel_options) aligner_p->set_kernel_option(opt);
+                    aligner_p->align_batch_device(d_seqs, d_offsets, i - first);
+                    const std::string_view text = aligner_p->format_batch_tsv(r.names, r.name_offsets + first, i - first, annotation ? &label_names : nullptr);
+                    std::cout.write(text.data(), (std::streamsize)text.size());
+                    ++n_batches;
+                }
+                n_queries += r.n_records;
+                memmove(buf.p, buf.p + r.consumed, have - r.consumed);
+                have -= r.consumed;
+                file_at += r.consumed;
+                if (eof) break;
+            }
+            close(fd);
+            std::cout.flush();
+            if (report_time && !status) {
+                const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                fprintf(stderr, "mgx_align: %zu queries in %zu batches, 1 worker(s), %.3f s in the read-parse-align loop (%.0f queries/s)\n",
+                        n_queries, n_batches, sec, sec > 0 ? (double)n_queries / sec : 0.0);
+            }
+            return status;
+        }
         std::vector<IDBGAligner::Query> all;
         if (!read_records(argv[2], &all)) { fprintf(stderr, "cannot open %s\n", argv[2]); return 1; }
         if (map_mode) {
