@@ -48,6 +48,9 @@ struct EmuRun {
     uint64_t seedlane_done = 0, seedlane_ran = 0;       // MGX_EMU_SEEDLANE: reads the lane-per-read seeder finished; whether it ran
     uint64_t seedlane_bail[16] = { 0 };
     std::vector<uint8_t> lane_reason;          // per read: 0 = finished by the lane path, else the code
+    // per read, two bytes: the SL_LEAVE code the seeder's first pass left it with (0: that pass seeded it), the second pass's
+    // (0: that pass seeded it, or never saw it); empty if the seeder did not run
+    std::vector<uint8_t> seedlane_reason;
 };
 // the label matrix in the device's row-major form (mgx_annot.hip: head word = count:16 | single label or offset into more[])
 struct EmuAnno {
@@ -470,6 +473,7 @@ void *emu_align_anno(void *gh, void *anno, const mgx_config *config, const mgx_l
                 std::vector<uint64_t> sq(2 * qwords);
                 std::vector<uint32_t> scnt(16);
                 R->seedlane_ran = 1;
+                R->seedlane_reason.assign(2 * n, 0);
                 // (MGX_EMU_SEEDLANE_ONE=1: the first pass only)
                 const bool two = !(getenv("MGX_EMU_SEEDLANE_ONE") && atoi(getenv("MGX_EMU_SEEDLANE_ONE")) == 1);
                 std::vector<uint64_t> todo(n), left;
@@ -496,6 +500,7 @@ void *emu_align_anno(void *gh, void *anno, const mgx_config *config, const mgx_l
                         } else {
                             left.push_back(i);
                             why1[i] = (uint8_t)so.reason;
+                            R->seedlane_reason[2 * i + ps] = (uint8_t)so.reason;
                             if (ps || !two) ++R->seedlane_bail[so.reason & 15u];
                         }
                         R->stats.rank_lines += so.ctr.rank_lines; R->stats.select_lines += so.ctr.select_lines; R->stats.bit_lines += so.ctr.bit_lines;
@@ -693,6 +698,12 @@ void emu_seedlane_stats(void *r, uint64_t *out18) {
     const EmuRun *R = static_cast<EmuRun *>(r);
     out18[0] = R->seedlane_ran; out18[1] = R->seedlane_done;
     for (int x = 0; x < 16; ++x) out18[2 + x] = R->seedlane_bail[x];
+}
+// per read two bytes (EmuRun::seedlane_reason); returns 0 if the seeder did not run
+int emu_seedlane_reasons(void *r, uint8_t *out, uint64_t n) {
+    auto &v = static_cast<EmuRun *>(r)->seedlane_reason;
+    for (uint64_t i = 0; i < 2 * n && i < v.size(); ++i) out[i] = v[i];
+    return v.empty() ? 0 : 1;
 }
 void emu_lane_bails(void *r, uint64_t *out32) { for (int x = 0; x < 32; ++x) out32[x] = static_cast<EmuRun *>(r)->lane_bail[x]; }
 void emu_stats(void *r, uint64_t *out8) {

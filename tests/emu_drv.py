@@ -207,6 +207,18 @@ class EmuRun:
         L().emu_seedlane_stats(self.r, a)
         return bool(a[0]), int(a[1]), {i: int(a[2 + i]) for i in range(16) if a[2 + i]}
 
+    def seedlane_reasons(self):
+        """MGX_EMU_SEEDLANE=1 runs, per read (final, pass1, pass2): pass1 = the SL_LEAVE code (seed_lane.hpp) the seeder's first
+        pass left the read with, 0 if that pass seeded it; pass2 = the second pass's, 0 if it seeded the read or never saw it;
+        final = 0 if a lane seeded the read, else the code it went to the wave-per-read seeder with — what seedlane_stats()
+        counts (pass1 under MGX_EMU_SEEDLANE_ONE=1).  None if the seeder did not run."""
+        a = (C.c_uint8 * max(1, 2 * self.n))()
+        L().emu_seedlane_reasons.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64]
+        if not L().emu_seedlane_reasons(self.r, a, self.n):
+            return None
+        one = os.environ.get("MGX_EMU_SEEDLANE_ONE") == "1"
+        return [(a[2 * i] if one else a[2 * i + 1] if a[2 * i] else 0, a[2 * i], a[2 * i + 1]) for i in range(self.n)]
+
     def lane_bails(self):
         """reads the lane-per-read path sent on to the wave program, by LANE_BAIL code (lane_read.hpp)"""
         a = (C.c_uint64 * 32)()

@@ -19,10 +19,10 @@ def seedlane_env(monkeypatch):
     monkeypatch.setenv("MGX_EMU_SEEDLANE", "1")
 
 
-def run(g, cfg, reads, mode=0):
+def run(g, cfg, reads, mode=0, limits=None):
     o = orc.AlignRun(g, cfg, reads, validate=False)
     assert o.error == "", o.error
-    e = emu_drv.EmuRun(emu_drv.EmuGraph(g, mode=mode), cfg, reads)
+    e = emu_drv.EmuRun(emu_drv.EmuGraph(g, mode=mode), cfg, reads, limits=limits)
     assert e.error == "", e.error
     got, status = e.results()
     assert all(s == 0 for s in status)
