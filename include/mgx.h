@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_read_parser_* / mgx_parse_reads / mgx_parse_kernel_launch_counts (FASTA / FASTQ text to
+#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
+                                * `align --map`, written by kernels); before that mgx_read_parser_* / mgx_parse_reads / mgx_parse_kernel_launch_counts (FASTA / FASTQ text to
                                 * read batches on the device); before that mgx_format_tsv_batch / mgx_format_kernel_launch_counts (the TSV text of a batch, written
                                 * by kernels); before that mgx_map_summary_batch / mgx_map_present / mgx_format_map / mgx_map_kernel_launch_counts
                                 * (`align --map`: per-read k-mer counts, presence, --align-length < k);
@@ -341,7 +342,10 @@ typedef struct mgx_map_summary {
     const uint64_t *node_begin;       /* n_queries + 1; NULL unless MGX_MAP_WANT_NODES */
     const uint64_t *nodes;            /* the map_to_nodes result, rules above */
 } mgx_map_summary;
-enum { MGX_MAP_WANT_NODES = 1 };
+/* MGX_MAP_KEEP_NODES: k_map_summary writes the 64-bit node array to device memory, where mgx_format_map_batch reads it; nothing
+ * more is copied to the host than without a flag (node_begin and nodes stay NULL, out4[3] of mgx_map_kernel_launch_counts does
+ * not move).  MGX_MAP_WANT_NODES leaves the array on the device as well. */
+enum { MGX_MAP_WANT_NODES = 1, MGX_MAP_KEEP_NODES = 2 };
 int mgx_map_summary_batch(mgx_aligner *a, const char *seqs, const uint64_t *offsets, uint64_t n_queries,
                           int seqs_on_device, uint32_t map_length /* 0 = k; > k: MGX_ERR_INVALID */,
                           uint32_t flags, mgx_map_summary *out);
@@ -563,6 +567,26 @@ int mgx_format_tsv_batch(mgx_aligner *a, const char *headers, const uint64_t *he
 /* Test hook: out4 = launches of the size kernel, launches of the write kernel, queries whose line was formatted on the host
  * (capacity retries), bytes copied device-to-host by mgx_format_tsv_batch — since the library was loaded. */
 void mgx_format_kernel_launch_counts(uint64_t *out4);
+/*
+ * The text of `align --map` for a whole batch, written on the device (csrc/map_format.hpp, csrc/mgx_mapfmt.hip):
+ * byte for byte what mgx_format_map gives query by query, for the batch mgx_map_summary_batch ran last on this handle, with that
+ * call's map_length, n_queries and reads.  format: MGX_MAP_FMT_*; MGX_MAP_FMT_NODES needs a summary run with MGX_MAP_KEEP_NODES
+ * (or _WANT_NODES).  headers / header_offsets: host arrays as for mgx_format_tsv_batch (n_queries + 1 offsets; header bytes are
+ * copied as they are, up to the offset — no NUL ends one).  Query bytes are printed as they came: nothing is normalised.
+ * discovery_fraction: as for mgx_map_present; the host tabulates that function's double expressions per k-mer count and the
+ * kernels compare integers, so presence is mgx_map_present's for every query.
+ * The views are pinned host memory owned by the handle, valid until the next batch or format call on it.  With seqs_on_device
+ * != 0 in the summary call the caller's seqs / offsets must still be valid.
+ *   - Device-to-host copies: the text, the n_queries + 1 offsets and 16 bytes of counters (the text's size and a reserved
+ *     word, in one copy).  Counts and nodes do not travel.
+ *   - MGX_ERR_INVALID, named in mgx_last_error: a null argument; an unknown format; no summary batch staged — never run, or
+ *     mgx_align_batch_device / mgx_map_batch (any other batch call) ran since; MGX_MAP_FMT_NODES when the summary kept no nodes.
+ */
+int mgx_format_map_batch(mgx_aligner *a, const char *headers, const uint64_t *header_offsets, int format,
+                         double discovery_fraction, mgx_text *out);
+/* Test hook: out4 = launches of k_mapfmt_size, launches of k_mapfmt_write, bytes copied device-to-host, bytes copied
+ * host-to-device (headers, header offsets, the threshold table) by mgx_format_map_batch — since the library was loaded. */
+void mgx_format_map_kernel_launch_counts(uint64_t *out4);
 
 /* ---- FASTA / FASTQ text to read batches, parsed on the device --------------------------------------------
  * mgx_parse_reads turns the bytes of a FASTA / FASTQ file (plain text: gzip stays with the caller) into the arrays the calls

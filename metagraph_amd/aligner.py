@@ -233,27 +233,47 @@ class Aligner:
             out.append(([m.nodes_fwd[i] for i in range(b, e)], [m.nodes_rc[i] for i in range(b, e)]))
         return out
 
-    def map_summary(self, queries, map_length=0, want_nodes=False):
+    def map_summary(self, queries, map_length=0, want_nodes=False, keep_nodes=False):
         """`align --map` (mgx_map_summary_batch): DeBruijnGraph::map_to_nodes of every query summarised on the device.
         -> list of (n_discovered, n_kmers, n_unique); with want_nodes: (that list, list of node lists).  map_length 0 = k,
-        0 < L < k = the windows of --align-length L.  The view itself is kept in self.last_map_summary for format_map."""
-        blob, offs = pack_queries(queries)
+        0 < L < k = the windows of --align-length L.  The view itself is kept in self.last_map_summary for format_map.
+        keep_nodes: the node array stays in device memory for format_map_batch(.., MGX_MAP_FMT_NODES); nothing more comes to
+        the host.  queries: a list of str / bytes, or (seqs, offsets, n) device pointers (ParsedReads.device_slice)."""
+        flags = (capi.MGX_MAP_WANT_NODES if want_nodes else 0) | (capi.MGX_MAP_KEEP_NODES if keep_nodes else 0)
         m = capi.MapSummary()
-        _check(capi.lib().mgx_map_summary_batch(self.h, blob, offs.ctypes.data, len(queries), 0, map_length,
-                                                capi.MGX_MAP_WANT_NODES if want_nodes else 0, C.byref(m)))
+        if isinstance(queries, tuple):
+            seqs, offsets, n_queries = queries
+            _check(capi.lib().mgx_map_summary_batch(self.h, seqs, offsets, n_queries, 1, map_length, flags, C.byref(m)))
+        else:
+            blob, offs = pack_queries(queries)
+            n_queries = len(queries)
+            _check(capi.lib().mgx_map_summary_batch(self.h, blob, offs.ctypes.data, n_queries, 0, map_length, flags, C.byref(m)))
         self.last_map_summary = m
-        counts = [(m.counts[q].n_discovered, m.counts[q].n_kmers, m.counts[q].n_unique) for q in range(len(queries))]
+        counts = [(m.counts[q].n_discovered, m.counts[q].n_kmers, m.counts[q].n_unique) for q in range(n_queries)]
         if not want_nodes:
             return counts
-        nb = np.ctypeslib.as_array(m.node_begin, shape=(len(queries) + 1,))
+        nb = np.ctypeslib.as_array(m.node_begin, shape=(n_queries + 1,))
         nodes = np.ctypeslib.as_array(m.nodes, shape=(max(1, int(nb[-1])),))
-        return counts, [nodes[int(nb[q]):int(nb[q + 1])].tolist() for q in range(len(queries))]
+        return counts, [nodes[int(nb[q]):int(nb[q + 1])].tolist() for q in range(n_queries)]
 
     def map_present(self, counts, query_len, map_length=0, discovery_fraction=0.7):
         return map_present(counts, query_len, self.graph.k, map_length, discovery_fraction)
 
     def format_map(self, summary, qi, header, query, fmt, map_length=0, discovery_fraction=0.7):
         return format_map(summary, qi, header, query, self.graph.k, fmt, map_length, discovery_fraction)
+
+    def format_map_batch(self, headers, fmt, discovery_fraction=0.7):
+        """mgx_format_map_batch: the `align --map` text of the batch map_summary ran last, written by kernels (fmt =
+        capi.MGX_MAP_FMT_*; MGX_MAP_FMT_NODES after map_summary(..., keep_nodes=True)).  headers: one str / bytes per query, or
+        the (bytes, offsets) pair of ParsedReads.names_of.  -> (bytes of all queries' text in query order, numpy uint64 array of
+        len(headers) + 1 offsets)."""
+        blob, hoff, n_headers = _pack_headers(headers)
+        t = capi.Text()
+        _check(capi.lib().mgx_format_map_batch(self.h, blob, hoff.ctypes.data, fmt, discovery_fraction, C.byref(t)))
+        if t.n_queries != n_headers:
+            raise ValueError("format_map_batch: %d headers for a batch of %d queries" % (n_headers, t.n_queries))
+        lb = np.ctypeslib.as_array(t.line_begin, shape=(n_headers + 1,)).copy()
+        return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
 
     def set_pipeline(self, name):
         """Kernel selection: 'split8' (the name of the one pipeline: accepted, selects nothing), 'general' / 'chain'
@@ -292,15 +312,7 @@ class Aligner:
         """mgx_format_tsv_batch: the TSV text of the batch align_device / align_batch ran last, written by kernels.
         headers: one str / bytes per query; label_names: names of labels 0 .. len - 1 (label-aware aligners; others print as
         numbers).  -> (bytes of all lines in query order, numpy uint64 array of len(headers) + 1 line offsets)."""
-        if isinstance(headers, tuple) and len(headers) == 2 and isinstance(headers[1], np.ndarray):
-            blob, hoff = headers                   # the flat arrays of ParsedReads.names_of: bytes, uint64 offsets from 0
-            n_headers = len(hoff) - 1
-        else:
-            hs = [h if isinstance(h, bytes) else h.encode("latin-1") for h in headers]
-            hoff = np.zeros(len(hs) + 1, dtype=np.uint64)
-            if hs:
-                hoff[1:] = np.cumsum([len(h) for h in hs])
-            blob, n_headers = b"".join(hs), len(hs)
+        blob, hoff, n_headers = _pack_headers(headers)
         names = [n if isinstance(n, bytes) else n.encode() for n in (label_names or [])]
         arr = (C.c_char_p * len(names))(*names) if names else None
         t = capi.Text()
@@ -309,6 +321,18 @@ class Aligner:
             raise ValueError("format_tsv_batch: %d headers for a batch of %d queries" % (n_headers, t.n_queries))
         lb = np.ctypeslib.as_array(t.line_begin, shape=(n_headers + 1,)).copy()
         return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+
+
+def _pack_headers(headers):
+    """-> (bytes, uint64 offsets from 0, count) of a list of headers, or of the flat (bytes, offsets) pair of ParsedReads.names_of"""
+    if isinstance(headers, tuple) and len(headers) == 2 and isinstance(headers[1], np.ndarray):
+        blob, hoff = headers
+        return blob, hoff, len(hoff) - 1
+    hs = [h if isinstance(h, bytes) else h.encode("latin-1") for h in headers]
+    hoff = np.zeros(len(hs) + 1, dtype=np.uint64)
+    if hs:
+        hoff[1:] = np.cumsum([len(h) for h in hs])
+    return b"".join(hs), hoff, len(hs)
 
 
 class ParsedReads:
@@ -391,6 +415,14 @@ def format_kernel_launch_counts():
     device-to-host by format_tsv_batch) since the library was loaded"""
     out = (C.c_uint64 * 4)()
     capi.lib().mgx_format_kernel_launch_counts(out)
+    return tuple(int(x) for x in out)
+
+
+def format_map_kernel_launch_counts():
+    """mgx_format_map_kernel_launch_counts -> (size kernel launches, write kernel launches, bytes copied device-to-host, bytes
+    copied host-to-device by format_map_batch) since the library was loaded"""
+    out = (C.c_uint64 * 4)()
+    capi.lib().mgx_format_map_kernel_launch_counts(out)
     return tuple(int(x) for x in out)
 
 

@@ -94,6 +94,7 @@ class Reads(C.Structure):
 
 MGX_READS_FASTA, MGX_READS_FASTQ = 1, 2
 MGX_MAP_WANT_NODES = 1
+MGX_MAP_KEEP_NODES = 2
 MGX_MAP_FMT_NODES, MGX_MAP_FMT_COUNT_KMERS, MGX_MAP_FMT_QUERY_PRESENCE, MGX_MAP_FMT_FILTER_PRESENT = 0, 1, 2, 3
 
 
@@ -296,6 +297,9 @@ def lib():
     L.mgx_format_tsv_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Text)]
     L.mgx_format_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.mgx_format_kernel_launch_counts.restype = None
+    L.mgx_format_map_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(Text)]
+    L.mgx_format_map_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_format_map_kernel_launch_counts.restype = None
     L.mgx_read_parser_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_read_parser_destroy.argtypes = [C.c_void_p]
     L.mgx_read_parser_destroy.restype = None

@@ -15,6 +15,7 @@ constexpr size_t MGX_SEED_LANE_PARAMS_BYTES = 824;      // sizeof(SeedLaneParams
 constexpr size_t MGX_DEV_GRAPH_BYTES = 160;             // sizeof(DevGraph), dev_graph.hpp
 constexpr size_t MGX_FORMAT_ARGS_BYTES = 128;           // sizeof(TfBatch), tsv_format.hpp
 constexpr size_t MGX_PARSE_ARGS_BYTES = 144;            // sizeof(RpChunk), reads_parse.hpp
+constexpr size_t MGX_MAPFMT_ARGS_BYTES = 120;           // sizeof(MfBatch), map_format.hpp
 
 struct mgx_annotation;
 
@@ -77,6 +78,11 @@ uint32_t mgx_map_summary_short_max(void);
 int mgx_launch_format_size(const void *args, void *stream);
 int mgx_launch_format_write(const void *args, void *stream);
 int mgx_launch_format_patch(uint64_t *line_len, const uint32_t *queries, const uint64_t *lens, uint32_t m, void *stream);
+
+// mgx_mapfmt.hip: the text of `align --map` for a batch (map_format.hpp).  args: an MfBatch (host memory).  size: line_len[q] for
+// every query; write: the text at text + line_begin[q].
+int mgx_launch_mapfmt_size(const void *args, void *stream);
+int mgx_launch_mapfmt_write(const void *args, void *stream);
 
 // mgx_parse.hip: FASTA / FASTQ text to read batches (reads_parse.hpp).  args: an RpChunk (host memory).  count: the '\n' mask and
 // count of every 64-byte span; table: line_begin[] from the masks and the scanned counts; classify: what every line adds (items);

@@ -27,6 +27,7 @@
 #include "seed_lane.hpp"
 #include "kernel_units.hpp"
 #include "tsv_format.hpp"
+#include "map_format.hpp"
 
 using namespace mgx;
 static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES && sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES
@@ -600,6 +601,16 @@ struct mgx_aligner {
     DevBuf ms_counts, ms_nodes, ms_sorted;       // mgx_map_summary_batch: the 12-byte records, the merged node array, the long form's scratch
     std::vector<mgx_map_counts> h_ms_counts;
     std::vector<uint64_t> h_ms_nodes;
+    // the batch mgx_map_summary_batch ran last, for mgx_format_map_batch: the stage_batch call it was (0: none, or the call failed —
+    // every other batch call stages again and so ends it), its reads (device pointers), map_length, longest read, and whether
+    // ms_nodes holds its node array
+    uint64_t ms_generation = 0;
+    const char *ms_d_seqs = nullptr;
+    const uint64_t *ms_d_offsets = nullptr;
+    uint32_t ms_map_length = 0, ms_lmax = 0;
+    bool ms_have_nodes = false;
+    DevBuf mf_threshold;                         // mgx_format_map_batch: the presence threshold per k-mer count
+    std::vector<uint64_t> h_mf_threshold;        // ... its host copy (the handle's: an asynchronous upload may outlive the call that failed)
     // mgx_format_tsv_batch: headers, their offsets, label names (bytes, then the n + 1 begins), line lengths, line_begin (n + 1, then
     // the capacity counter), the text, the capacity list, the host-formatted lines' (query, length) pairs
     DevBuf tf_headers, tf_header_offsets, tf_names, tf_len, tf_begin, tf_text, tf_cap, tf_patch;
@@ -914,7 +925,7 @@ static int aligner_create(const mgx_graph *g, const mgx_config *config, const mg
                        &A->cursors, &A->d_stats, &A->d_stats_map, &A->scan_tmp, &A->dbg_seeds, &A->seed_hdr, &A->seed_stream, &A->work_key,
                        &A->work_key_sorted, &A->order_in, &A->order, &A->sort_tmp, &A->retry_list, &A->resume_pool[0], &A->resume_pool[1],
                        &A->retry_list2, &A->retry_key[0], &A->retry_key[1], &A->lane_scratch, &A->lane_params, &A->lane_bail, &A->lane_hist, &A->seedlane_scratch, &A->seedlane_params,
-                       &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted, &A->tf_headers, &A->tf_header_offsets,
+                       &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted, &A->mf_threshold, &A->tf_headers, &A->tf_header_offsets,
                        &A->tf_names, &A->tf_len, &A->tf_begin, &A->tf_text, &A->tf_cap, &A->tf_patch })
         b->pooled = true;
     {
@@ -1731,7 +1742,8 @@ int mgx_map_summary_batch(mgx_aligner *A, const char *seqs, const uint64_t *offs
     if (!A || !seqs || !offsets || !out) return fail(MGX_ERR_INVALID, "null argument");
     const uint32_t k = A->graph->g.k;
     if (map_length > k) return fail(MGX_ERR_INVALID, "map_length %u exceeds k = %u", map_length, k);
-    if (flags & ~(uint32_t)MGX_MAP_WANT_NODES) return fail(MGX_ERR_INVALID, "unknown flags %u", flags);
+    A->ms_generation = 0;
+    if (flags & ~(uint32_t)(MGX_MAP_WANT_NODES | MGX_MAP_KEEP_NODES)) return fail(MGX_ERR_INVALID, "unknown flags %u", flags);
     const bool sub_k = map_length != 0 && map_length < k;
     const uint32_t mode = A->graph->mode;
     // the reference casts the CanonicalDBG wrapper to a DBGSuccinct here (cli/align.cpp:117 after :347): undefined, so refused
@@ -1740,11 +1752,12 @@ int mgx_map_summary_batch(mgx_aligner *A, const char *seqs, const uint64_t *offs
     HIP_TRY(hipSetDevice(A->graph->device));
     const char *d_seqs; const uint64_t *d_offsets; uint32_t Lmax;
     if (int rc = stage_batch(A, seqs, offsets, n, on_device, &d_seqs, &d_offsets, &Lmax, sub_k ? map_length : 0)) return rc;
-    const bool want_nodes = (flags & MGX_MAP_WANT_NODES) != 0;
+    const bool want_nodes = (flags & MGX_MAP_WANT_NODES) != 0;                               // the node array comes to the host
+    const bool keep_nodes = want_nodes || (flags & MGX_MAP_KEEP_NODES) != 0;                 // k_map_summary writes it to ms_nodes
     const uint32_t window = sub_k ? map_length : k;
     const bool any_long = Lmax >= window && Lmax - window + 1 > mgx_map_summary_short_max();
     if (int rc = A->ms_counts.ensure((n + 1) * sizeof(mgx_map_counts))) return rc;
-    if (want_nodes) if (int rc = A->ms_nodes.ensure((A->total_kmers + 1) * 8)) return rc;
+    if (keep_nodes) if (int rc = A->ms_nodes.ensure((A->total_kmers + 1) * 8)) return rc;
     if (any_long) if (int rc = A->ms_sorted.ensure((A->total_kmers + 1) * 4)) return rc;
     int rule = MGX_MODE_BASIC;
     if (sub_k) {
@@ -1758,7 +1771,7 @@ int mgx_map_summary_batch(mgx_aligner *A, const char *seqs, const uint64_t *offs
     }
     for (int long_form = 0; long_form <= (any_long ? 1 : 0); ++long_form) {
         if (mgx_launch_map_summary(A->node_begin.as<uint64_t>(), A->nodes_fwd.as<uint32_t>(), A->nodes_rc.as<uint32_t>(), A->ms_sorted.as<uint32_t>(),
-                                   A->ms_counts.p, want_nodes ? A->ms_nodes.as<uint64_t>() : nullptr, A->graph->g.valid, n,
+                                   A->ms_counts.p, keep_nodes ? A->ms_nodes.as<uint64_t>() : nullptr, A->graph->g.valid, n,
                                    (uint32_t)A->graph->g.n, rule, long_form, A->hstream))
             return fail(MGX_ERR_NO_DEVICE, "k_map_summary launch failed");
         if (n) ++g_map_summary_counts[long_form];
@@ -1780,6 +1793,9 @@ int mgx_map_summary_batch(mgx_aligner *A, const char *seqs, const uint64_t *offs
         out->node_begin = A->m_node_begin.data();
         out->nodes = A->h_ms_nodes.data();
     }
+    A->ms_generation = A->stage_generation;
+    A->ms_d_seqs = d_seqs; A->ms_d_offsets = d_offsets;
+    A->ms_map_length = map_length; A->ms_lmax = Lmax; A->ms_have_nodes = keep_nodes;
     return MGX_OK;
 }
 void mgx_map_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_map_summary_counts[x].load(); }
@@ -2303,6 +2319,106 @@ int mgx_format_tsv_batch(mgx_aligner *A, const char *headers, const uint64_t *he
     if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
     HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
     for (size_t t = 0; t < todo.size(); ++t) memcpy(A->h_text + A->h_line_begin[todo[t]], host_lines[t].data(), host_lines[t].size());
+    out->text = A->h_text;
+    return MGX_OK;
+}
+
+// ---- the text of `align --map` for a batch, written by kernels (map_format.hpp, mgx_mapfmt.hip) -------------
+enum { MF_CNT_SIZE = 0, MF_CNT_WRITE, MF_CNT_D2H_BYTES, MF_CNT_H2D_BYTES };
+static std::atomic<uint64_t> g_mapfmt_counts[4];        // mgx_format_map_kernel_launch_counts
+void mgx_format_map_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_mapfmt_counts[x].load(); }
+
+int mgx_format_map_batch(mgx_aligner *A, const char *headers, const uint64_t *header_offsets, int format, double discovery_fraction,
+                         mgx_text *out) {
+    static_assert(sizeof(MfBatch) == MGX_MAPFMT_ARGS_BYTES, "MfBatch differs from what mgx_mapfmt.hip takes");
+    static_assert(MF_NODES == MGX_MAP_FMT_NODES && MF_COUNT_KMERS == MGX_MAP_FMT_COUNT_KMERS && MF_QUERY_PRESENCE == MGX_MAP_FMT_QUERY_PRESENCE
+                  && MF_FILTER_PRESENT == MGX_MAP_FMT_FILTER_PRESENT, "map formats");
+    if (!A || !out || !headers || !header_offsets) return fail(MGX_ERR_INVALID, "mgx_format_map_batch: null argument");
+    if (format != MGX_MAP_FMT_NODES && format != MGX_MAP_FMT_COUNT_KMERS && format != MGX_MAP_FMT_QUERY_PRESENCE && format != MGX_MAP_FMT_FILTER_PRESENT)
+        return fail(MGX_ERR_INVALID, "mgx_format_map_batch: unknown format %d", format);
+    if (!A->ms_generation)
+        return fail(MGX_ERR_INVALID, "mgx_format_map_batch: no summary batch staged: mgx_map_summary_batch has not run on this handle");
+    if (A->ms_generation != A->stage_generation)
+        return fail(MGX_ERR_INVALID, "mgx_format_map_batch: no summary batch staged: mgx_align_batch_device or mgx_map_batch ran on this "
+                                     "handle after mgx_map_summary_batch");
+    if (format == MGX_MAP_FMT_NODES && !A->ms_have_nodes)
+        return fail(MGX_ERR_INVALID, "mgx_format_map_batch: MGX_MAP_FMT_NODES needs the node array: run mgx_map_summary_batch with "
+                                     "MGX_MAP_KEEP_NODES (or MGX_MAP_WANT_NODES)");
+    const uint64_t n = A->n_reads;
+    A->h_line_begin.assign(n + 1, 0);
+    out->n_queries = n; out->text = A->h_text ? A->h_text : ""; out->line_begin = A->h_line_begin.data();
+    if (!n) return MGX_OK;
+    if (n >= 0x7FFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_map_batch: more than 2^31 - 2 queries in a batch");
+    if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
+    HIP_TRY(hipSetDevice(A->graph->device));
+    auto d2h = [&](void *dst, const void *src, size_t bytes) {
+        g_mapfmt_counts[MF_CNT_D2H_BYTES] += bytes;
+        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    auto h2d = [&](void *dst, const void *src, size_t bytes) {
+        g_mapfmt_counts[MF_CNT_H2D_BYTES] += bytes;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, A->hstream);
+    };
+    const uint32_t k = A->graph->g.k, map_length = A->ms_map_length;
+    const bool sub_k = map_length != 0 && map_length < k;
+    const uint32_t window = sub_k ? map_length : k;
+    // the presence threshold for every k-mer count a read of this batch can have, by mgx_map_present's own expressions (the same
+    // compiler, the same flags, the same doubles): the kernels compare integers
+    const uint32_t max_kmers = A->ms_lmax >= window ? A->ms_lmax - window + 1 : 0;
+    const bool presence = format == MGX_MAP_FMT_QUERY_PRESENCE || format == MGX_MAP_FMT_FILTER_PRESENT;
+    std::vector<uint64_t> &threshold = A->h_mf_threshold;
+    HIP_TRY(hipStreamSynchronize(A->hstream));       // (no earlier upload still reads the table)
+    threshold.assign(presence ? (size_t)max_kmers + 1 : 1, 0);
+    if (presence)
+        for (size_t n_kmers = 0; n_kmers <= max_kmers; ++n_kmers)
+            threshold[n_kmers] = mf_threshold_host(n_kmers, discovery_fraction, sub_k);
+    const uint64_t header_bytes = header_offsets[n];
+    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
+    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->mf_threshold.ensure(threshold.size() * 8)) return rc;
+    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
+    if (header_bytes) HIP_TRY(h2d(A->tf_headers.p, headers, header_bytes));
+    HIP_TRY(h2d(A->tf_header_offsets.p, header_offsets, (n + 1) * 8));
+    HIP_TRY(h2d(A->mf_threshold.p, threshold.data(), threshold.size() * 8));
+    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
+    MfBatch b;
+    memset(&b, 0, sizeof(b));
+    b.counts = A->ms_counts.as<uint32_t>(); b.nodes = A->ms_nodes.as<uint64_t>(); b.node_begin = A->node_begin.as<uint64_t>();
+    b.seqs = A->ms_d_seqs; b.offsets = A->ms_d_offsets;
+    b.headers = A->tf_headers.as<char>(); b.header_offsets = A->tf_header_offsets.as<uint64_t>();
+    b.threshold = A->mf_threshold.as<uint64_t>();
+    b.line_len = d_len; b.line_begin = d_begin;
+    b.n_queries = n; b.max_kmers = presence ? max_kmers : 0; b.k = k; b.window = window; b.sub_k = sub_k ? 1u : 0u; b.format = format;
+    // pass 1: the text lengths (d_len[n] = 0 closes the scan); the scan gives line_begin
+    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
+    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
+    HIP_TRY((hipError_t)mgx_launch_mapfmt_size(&b, A->hstream));
+    ++g_mapfmt_counts[MF_CNT_SIZE];
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+    if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+    // the counters, one copy like mgx_format_tsv_batch's: the text's bytes and a second word that is reserved (0: this formatter
+    // leaves no line to the host)
+    uint64_t counters[2] = { 0, 0 };
+    HIP_TRY(d2h(counters, d_begin + n, 16));
+    // pass 2: the text
+    const uint64_t text_bytes = counters[0];
+    if (int rc = A->tf_text.ensure(text_bytes + 16)) return rc;
+    if (text_bytes + 1 > A->h_text_bytes) {
+        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
+        const size_t want = text_bytes + text_bytes / 8 + 4096;
+        void *p = nullptr;
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(MGX_ERR_OOM, "hipHostMalloc(%zu) failed", want); }
+        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
+    }
+    b.text = A->tf_text.as<char>();
+    HIP_TRY((hipError_t)mgx_launch_mapfmt_write(&b, A->hstream));
+    ++g_mapfmt_counts[MF_CNT_WRITE];
+    g_mapfmt_counts[MF_CNT_D2H_BYTES] += text_bytes;
+    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
+    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
     out->text = A->h_text;
     return MGX_OK;
 }

@@ -169,16 +169,37 @@ class HipGraphMapper {
     ~HipGraphMapper() { mgx_aligner_destroy(a_); }
     HipGraphMapper(const HipGraphMapper &) = delete;
     // The view of the whole batch (valid until the next call): counts per sequence and, with want_nodes, the node arrays.
-    // map_length: 0 = k; L < k = the windows of --align-length L (BASIC and CANONICAL graphs).
-    mgx_map_summary map_batch(const std::vector<std::string_view> &seqs, uint32_t map_length = 0, bool want_nodes = false) const {
+    // map_length: 0 = k; L < k = the windows of --align-length L (BASIC and CANONICAL graphs).  keep_nodes: the node array stays in
+    // device memory for format_batch(.., MGX_MAP_FMT_NODES) and nothing more comes to the host.
+    mgx_map_summary map_batch(const std::vector<std::string_view> &seqs, uint32_t map_length = 0, bool want_nodes = false, bool keep_nodes = false) const {
         std::string blob;
         std::vector<uint64_t> offsets(seqs.size() + 1, 0);
         for (size_t t = 0; t < seqs.size(); ++t) { blob.append(seqs[t].data(), seqs[t].size()); offsets[t + 1] = blob.size(); }
         if (blob.empty()) blob.push_back('\0');
         mgx_map_summary out{};
-        if (int rc = mgx_map_summary_batch(a_, blob.data(), offsets.data(), seqs.size(), 0, map_length, want_nodes ? MGX_MAP_WANT_NODES : 0, &out))
+        if (int rc = mgx_map_summary_batch(a_, blob.data(), offsets.data(), seqs.size(), 0, map_length,
+                                           (want_nodes ? MGX_MAP_WANT_NODES : 0u) | (keep_nodes ? MGX_MAP_KEEP_NODES : 0u), &out))
             throw std::runtime_error(std::string("mgx_map_summary_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
         return out;
+    }
+    // ... over reads that are in device memory already (HipReadParser::slice): n reads, offsets from 0
+    mgx_map_summary map_batch_device(const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t map_length, bool keep_nodes) const {
+        mgx_map_summary out{};
+        if (int rc = mgx_map_summary_batch(a_, d_seqs, d_offsets, n, 1, map_length, keep_nodes ? MGX_MAP_KEEP_NODES : 0, &out))
+            throw std::runtime_error(std::string("mgx_map_summary_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        return out;
+    }
+    // The text map_sequences_in_file prints for the batch mapped last, written on the device (mgx_format_map_batch): what
+    // mgx_format_map gives for every query, in query order.  names / name_offsets: the headers as flat arrays, `name_offsets`
+    // points at the batch's first record (n + 1 entries).  The view is the handle's and stays valid until its next batch.
+    std::string_view format_batch(const char *names, const uint64_t *name_offsets, uint64_t n, int format, double discovery_fraction) const {
+        std::vector<uint64_t> offsets(n + 1);
+        for (uint64_t t = 0; t <= n; ++t) offsets[t] = name_offsets[t] - name_offsets[0];
+        mgx_text text{};
+        if (int rc = mgx_format_map_batch(a_, names + name_offsets[0], offsets.data(), format, discovery_fraction, &text))
+            throw std::runtime_error(std::string("mgx_format_map_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        if (text.n_queries != n) throw std::runtime_error("mgx_format_map_batch: the handle's batch is not this one");
+        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
     }
     // std::vector<node_index> map_to_nodes(const DeBruijnGraph &, std::string_view) (sequence_graph.cpp)
     std::vector<uint64_t> map_to_nodes(std::string_view sequence) const {

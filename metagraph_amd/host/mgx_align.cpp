@@ -10,6 +10,14 @@
 //                             --align-length N (windows of N < k characters; 0 = k, above k: a warning and k);
 //                             --fwd-and-reverse (every record followed by its reverse complement under the same name).
 //                             Output in input order; no annotation is loaded in this mode
+//             [--map-on-device]  with --map: every batch is mapped with its node array left in device memory and its text is written
+//                             by kernels (mgx_format_map_batch) and printed with one write per batch; same bytes in every form.
+//                             With --parse-on-device in addition (not --format-on-device): the file is read in chunks and parsed by
+//                             kernels as for alignment (same grammar, same two exceptions), the reads are mapped from the parser's
+//                             device arrays — file bytes in, text bytes out; -p 1 and --devices 1 only, not with --fwd-and-reverse
+//                             (whose records are made on the host).  --parse-chunk-bytes and --time work as for alignment.
+//                             A third exception on this path: a name that holds a NUL byte is printed whole (the host path
+//                             and mgx_format_map cut a name at its first NUL)
 //             [--format-on-device]  the TSV text of every batch is written by kernels (mgx_format_tsv_batch) and printed with one write
 //                             per batch, instead of one host-built string per query; same bytes.  Not with --map or --rccl-gather
 //             [--parse-on-device]  with --format-on-device, -p 1 and --devices 1: the file is read in large chunks with read(2) into
@@ -18,7 +26,8 @@
 //                             where the parser follows kseq and read_records does not: a record with an empty name is printed
 //                             (read_records drops it), and in a CRLF file the '\r' is not part of the sequence (std::getline
 //                             keeps it).  Files outside the grammar: exit status 1 and the byte position.  Not with --map or
-//                             --rccl-gather
+//                             --rccl-gather (--map has --map-on-device, below, which takes --parse-on-device without
+//                             --format-on-device)
 //             [--devices D]   in-process multi-GPU: one graph replica per device, whole batches routed round-robin, no collective
 //             [--rccl-gather] with --devices D: one worker per device, batches in rounds of D; every round's device results are
 //                             gathered to device 0 over RCCL (mgx_gather_*: the C-ABI of north_star's "RCCL-over-xGMI only to
@@ -117,7 +126,7 @@ int main(int argc, char **argv) {
     mgx_limits lim;
     bool have_lim = false;
     int devices = 1;
-    bool rccl_gather = false, format_on_device = false, parse_on_device = false;
+    bool rccl_gather = false, format_on_device = false, parse_on_device = false, map_on_device = false;
     uint64_t parse_chunk_bytes = 256ull << 20;         // --parse-chunk-bytes N (test hook: several chunks from a small file)
     std::vector<const char *> anno_paths;
     std::vector<std::string> kernel_options;            // --kernel-option key=value: result-preserving kernel selection (A/B runs)
@@ -145,12 +154,24 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rccl-gather")) rccl_gather = true;
         else if (!strcmp(argv[i], "--format-on-device")) format_on_device = true;
         else if (!strcmp(argv[i], "--parse-on-device")) parse_on_device = true;
+        else if (!strcmp(argv[i], "--map-on-device")) map_on_device = true;
         else if (!strcmp(argv[i], "--parse-chunk-bytes") && i + 1 < argc) parse_chunk_bytes = std::max<uint64_t>(1, strtoull(argv[++i], nullptr, 10));
         else if (!strcmp(argv[i], "--time")) report_time = true;            // wall time of the align loop (batches -> results printed) on stderr
         else if (!strcmp(argv[i], "--canonical")) graph_mode = MGX_MODE_CANONICAL;
         else if (!strcmp(argv[i], "--primary")) graph_mode = MGX_MODE_PRIMARY;         // aligned through the CanonicalDBG wrapper
     }
-    if (parse_on_device && (map_mode || rccl_gather || !format_on_device || threads != 1 || devices != 1)) {
+    if (map_on_device && !map_mode) {
+        fprintf(stderr, "error: --map-on-device writes the text of --map on the device: it needs --map\n");
+        return 1;
+    }
+    // --map --map-on-device --parse-on-device: the parser's device arrays go to one mapper and its formatter
+    const bool map_parse_on_device = map_mode && map_on_device && parse_on_device && !format_on_device;
+    if (map_parse_on_device && (fwd_and_reverse || threads != 1 || devices != 1)) {
+        fprintf(stderr, "error: --map-on-device --parse-on-device maps the parser's device arrays on one device: %s\n",
+                fwd_and_reverse ? "not with --fwd-and-reverse (its records are made on the host)" : threads != 1 ? "with -p 1 only" : "with --devices 1 only");
+        return 1;
+    }
+    if (parse_on_device && !map_parse_on_device && (map_mode || rccl_gather || !format_on_device || threads != 1 || devices != 1)) {
         fprintf(stderr, "error: --parse-on-device hands the parser's device arrays to one aligner and its formatter: %s\n",
                 map_mode ? "not with --map" : rccl_gather ? "not with --rccl-gather" : !format_on_device ? "it needs --format-on-device"
                 : "with -p 1 and --devices 1 only");
@@ -207,6 +228,13 @@ int main(int argc, char **argv) {
             annotation = std::make_unique<HipAnnotation>(n_rows, col_begin, rows, 0);
         }
         if ((unsigned)devices > threads) threads = (unsigned)devices;                  // at least one worker per device
+        if (map_mode) {
+            // cli/align.cpp:351-355
+            if (align_length > k) { fprintf(stderr, "warning: Mapping to k-mers longer than k is not supported. Setting --align-length to %u\n", k); align_length = k; }
+            if (!align_length) align_length = k;
+        }
+        const int map_format = query_presence ? (filter_present ? MGX_MAP_FMT_FILTER_PRESENT : MGX_MAP_FMT_QUERY_PRESENCE)
+                               : count_kmers ? MGX_MAP_FMT_COUNT_KMERS : MGX_MAP_FMT_NODES;
         if (parse_on_device) {
             // file bytes in, TSV bytes out: read(2) into a pinned buffer, a parse per chunk (the unconsumed tail is carried over to
             // the next chunk), batches cut at the reference's rule from the parser's host copy of the offsets, aligned from
@@ -228,6 +256,11 @@ int main(int argc, char **argv) {
             parse_chunk_bytes = std::min<uint64_t>(parse_chunk_bytes, 0xF0000000ull);
             const HipBOSSGraph &graph = graphs.for_worker(0);
             HipReadParser parser(0);
+            std::unique_ptr<HipGraphMapper> mapper;
+            if (map_mode) {
+                mapper.reset(new HipGraphMapper(graph));
+                for (const std::string &opt : kernel_options) mapper->set_kernel_option(opt);
+            }
             const auto t0 = std::chrono::steady_clock::now();
             size_t have = 0, n_queries = 0, n_batches = 0;
             uint64_t file_at = 0;                      // the file position of buf[0]
@@ -258,6 +291,13 @@ int main(int argc, char **argv) {
                     while (i < r.n_records && r.host_offsets[i] - r.host_offsets[first] <= batch_size) ++i;
                     const char *d_seqs; const uint64_t *d_offsets;
                     parser.slice(first, i - first, &d_seqs, &d_offsets);
+                    if (map_mode) {
+                        mapper->map_batch_device(d_seqs, d_offsets, i - first, align_length, map_format == MGX_MAP_FMT_NODES);
+                        const std::string_view text = mapper->format_batch(r.names, r.name_offsets + first, i - first, map_format, discovery_fraction);
+                        std::cout.write(text.data(), (std::streamsize)text.size());
+                        ++n_batches;
+                        continue;
+                    }
                     std::unique_ptr<HipDBGAligner> aligner_p(annotation
                         ? new HipDBGAligner(graph, cfg, *annotation, have_lim ? &lim : nullptr)
                         : new HipDBGAligner(graph, cfg, have_lim ? &lim : nullptr));
@@ -277,17 +317,14 @@ int main(int argc, char **argv) {
             std::cout.flush();
             if (report_time && !status) {
                 const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                fprintf(stderr, "mgx_align: %zu queries in %zu batches, 1 worker(s), %.3f s in the read-parse-align loop (%.0f queries/s)\n",
-                        n_queries, n_batches, sec, sec > 0 ? (double)n_queries / sec : 0.0);
+                fprintf(stderr, "mgx_align: %zu queries in %zu batches, 1 worker(s), %.3f s in the read-parse-%s loop (%.0f queries/s)\n",
+                        n_queries, n_batches, sec, map_mode ? "map" : "align", sec > 0 ? (double)n_queries / sec : 0.0);
             }
             return status;
         }
         std::vector<IDBGAligner::Query> all;
         if (!read_records(argv[2], &all)) { fprintf(stderr, "cannot open %s\n", argv[2]); return 1; }
         if (map_mode) {
-            // cli/align.cpp:351-355
-            if (align_length > k) { fprintf(stderr, "warning: Mapping to k-mers longer than k is not supported. Setting --align-length to %u\n", k); align_length = k; }
-            if (!align_length) align_length = k;
             if (fwd_and_reverse) {                      // sequence_io.hpp:317-319
                 std::vector<IDBGAligner::Query> both;
                 for (auto &q : all) {
@@ -303,8 +340,7 @@ int main(int argc, char **argv) {
                 }
                 all.swap(both);
             }
-            const int format = query_presence ? (filter_present ? MGX_MAP_FMT_FILTER_PRESENT : MGX_MAP_FMT_QUERY_PRESENCE)
-                               : count_kmers ? MGX_MAP_FMT_COUNT_KMERS : MGX_MAP_FMT_NODES;
+            const int format = map_format;
             HipGraphMapper mapper(graphs.for_worker(0));
             for (const std::string &opt : kernel_options) mapper.set_kernel_option(opt);
             std::string line;
@@ -313,6 +349,16 @@ int main(int argc, char **argv) {
                 std::vector<std::string_view> seqs;
                 uint64_t bytes = 0;
                 for (; i < all.size() && bytes <= batch_size; ++i) { bytes += all[i].second.size(); seqs.emplace_back(all[i].second); }
+                if (map_on_device) {
+                    // the node array stays in device memory; the text of the whole batch comes back in one piece
+                    mapper.map_batch(seqs, align_length, false, format == MGX_MAP_FMT_NODES);
+                    std::string names;
+                    std::vector<uint64_t> name_offsets(seqs.size() + 1, 0);
+                    for (size_t t = 0; t < seqs.size(); ++t) { names += all[first + t].first.c_str(); name_offsets[t + 1] = names.size(); }
+                    const std::string_view text = mapper.format_batch(names.data(), name_offsets.data(), seqs.size(), format, discovery_fraction);
+                    std::cout.write(text.data(), (std::streamsize)text.size());
+                    continue;
+                }
                 const mgx_map_summary s = mapper.map_batch(seqs, align_length, format == MGX_MAP_FMT_NODES);
                 for (size_t t = 0; t < seqs.size(); ++t) {
                     const IDBGAligner::Query &q = all[first + t];
