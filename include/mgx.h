@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
+#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
+                                * batch, written by kernels); before that mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
                                 * `align --map`, written by kernels); before that mgx_read_parser_* / mgx_parse_reads / mgx_parse_kernel_launch_counts (FASTA / FASTQ text to
                                 * read batches on the device); before that mgx_format_tsv_batch / mgx_format_kernel_launch_counts (the TSV text of a batch, written
                                 * by kernels); before that mgx_map_summary_batch / mgx_map_present / mgx_format_map / mgx_map_kernel_launch_counts
@@ -587,6 +588,39 @@ int mgx_format_map_batch(mgx_aligner *a, const char *headers, const uint64_t *he
 /* Test hook: out4 = launches of k_mapfmt_size, launches of k_mapfmt_write, bytes copied device-to-host, bytes copied
  * host-to-device (headers, header offsets, the threshold table) by mgx_format_map_batch — since the library was loaded. */
 void mgx_format_map_kernel_launch_counts(uint64_t *out4);
+/*
+ * The `align --json` text of a range of a batch, written on the device (csrc/json_format.hpp, csrc/mgx_jsonfmt.hip).
+ * After mgx_align_batch_device (or mgx_align_batch) on this handle, under the rules of mgx_format_tsv_batch (the batch must still
+ * be the staged one; with seqs_on_device != 0 the caller's seqs / offsets must stay valid): the lines of queries first ..
+ * first + n of the staged batch, byte for byte what mgx_format_json gives for those queries in order with k = mgx_graph_k of the
+ * aligner's graph.  A query prints one line per alignment, a query without alignments the {"name":...,"sequence":""} line;
+ * out->line_begin[i] .. line_begin[i + 1] covers all lines of query first + i, out->n_queries = n.  headers / header_offsets: host
+ * arrays FOR THE RANGE, n + 1 offsets (header of query first + i = headers[header_offsets[i] .. header_offsets[i + 1]); no NUL ends
+ * one).  The range exists because JSON text is large (one mapping object per path node: 11.5 KB per 150-bp read measured on the
+ * benchmark graph, against ~350 bytes of TSV): a caller bounds
+ * the text of one call by formatting a staged batch in slices, and the slices' texts concatenated are the whole batch's.
+ * n == 0: MGX_OK, an empty text.  The views are pinned host memory owned by the handle, valid until the next batch or format call.
+ *   - Runs on the aligner's stream.  Device-to-host copies: the text, the n + 1 offsets and 16 bytes of counters; the result
+ *     records and the stream do not travel.
+ *   - Capacity statuses: as in mgx_format_tsv_batch — those queries alone are aligned again, their lines come from mgx_format_json
+ *     on the retried results and stand at their place; MGX_ERR_CAPACITY, naming the first such query, with retry_capacity=0 or
+ *     when the retry cures none.
+ *   - post_chain_alignments: MGX_ERR_UNSUPPORTED, naming post_chain_alignments (the reference throws "JSON output for chains not
+ *     supported").  A label-aware aligner is accepted: JSON carries no labels.
+ *   - MGX_ERR_INVALID, named in mgx_last_error: a null argument; first + n beyond the staged batch; no alignment batch staged
+ *     (never run, or a map / summary call ran since).
+ *   - "Byte for byte" holds for records as the extension kernels write them (csrc/json_format.hpp lists what the lanes take for
+ *     granted: offset < k; no insertion / clip run directly behind another one while nodes are left; num_matches <= the aligned
+ *     length; n_nodes no more than the CIGAR's node-consuming positions pay for).  The call formats the handle's own batch, so a
+ *     caller cannot hand it any other kind of record.
+ *   - MGX_ERR_OOM when the text buffer cannot be allocated; the message says how many bytes the range needs, so that the
+ *     caller can take a smaller range.
+ */
+int mgx_format_json_batch(mgx_aligner *a, const char *headers, const uint64_t *header_offsets,
+                          uint64_t first, uint64_t n, mgx_text *out);
+/* Test hook: out4 = launches of k_jsonfmt_size, launches of k_jsonfmt_write, queries whose lines were formatted on the host
+ * (capacity retries), bytes copied device-to-host by mgx_format_json_batch — since the library was loaded. */
+void mgx_format_json_kernel_launch_counts(uint64_t *out4);
 
 /* ---- FASTA / FASTQ text to read batches, parsed on the device --------------------------------------------
  * mgx_parse_reads turns the bytes of a FASTA / FASTQ file (plain text: gzip stays with the caller) into the arrays the calls

@@ -308,6 +308,21 @@ class Aligner:
         capi.lib().mgx_format_tsv(C.byref(res), qi, header.encode(), q, len(q), cfg.min_path_score, buf, n + 1)
         return buf.value.decode("latin-1")
 
+    def format_json_batch(self, headers, first=0, n=None):
+        """mgx_format_json_batch: the `align --json` text of queries first .. first + n (n = None: to the end) of the batch
+        align_device / align_batch ran last, written by kernels.  headers: one str / bytes per query OF THE RANGE, or the
+        (bytes, offsets) pair of ParsedReads.names_of(first, n).  JSON text is large (~60 bytes per path node): a caller bounds the
+        text of one call by its range; the ranges' texts concatenated are the whole batch's.
+        -> (bytes of the range's lines in query order, numpy uint64 array of n + 1 offsets: all lines of query first + i)."""
+        blob, hoff, n_headers = _pack_headers(headers)
+        n = n_headers if n is None else n
+        if n != n_headers:
+            raise ValueError("format_json_batch: %d headers for a range of %d queries" % (n_headers, n))
+        t = capi.Text()
+        _check(capi.lib().mgx_format_json_batch(self.h, blob, hoff.ctypes.data, first, n, C.byref(t)))
+        lb = np.ctypeslib.as_array(t.line_begin, shape=(n + 1,)).copy()
+        return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+
     def format_tsv_batch(self, headers, label_names=None):
         """mgx_format_tsv_batch: the TSV text of the batch align_device / align_batch ran last, written by kernels.
         headers: one str / bytes per query; label_names: names of labels 0 .. len - 1 (label-aware aligners; others print as
@@ -415,6 +430,14 @@ def format_kernel_launch_counts():
     device-to-host by format_tsv_batch) since the library was loaded"""
     out = (C.c_uint64 * 4)()
     capi.lib().mgx_format_kernel_launch_counts(out)
+    return tuple(int(x) for x in out)
+
+
+def format_json_kernel_launch_counts():
+    """mgx_format_json_kernel_launch_counts -> (size kernel launches, write kernel launches, queries formatted on the host, bytes
+    copied device-to-host by format_json_batch) since the library was loaded"""
+    out = (C.c_uint64 * 4)()
+    capi.lib().mgx_format_json_kernel_launch_counts(out)
     return tuple(int(x) for x in out)
 
 

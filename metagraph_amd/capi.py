@@ -300,6 +300,9 @@ def lib():
     L.mgx_format_map_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(Text)]
     L.mgx_format_map_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.mgx_format_map_kernel_launch_counts.restype = None
+    L.mgx_format_json_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(Text)]
+    L.mgx_format_json_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_format_json_kernel_launch_counts.restype = None
     L.mgx_read_parser_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_read_parser_destroy.argtypes = [C.c_void_p]
     L.mgx_read_parser_destroy.restype = None

@@ -16,6 +16,7 @@ constexpr size_t MGX_DEV_GRAPH_BYTES = 160;             // sizeof(DevGraph), dev
 constexpr size_t MGX_FORMAT_ARGS_BYTES = 128;           // sizeof(TfBatch), tsv_format.hpp
 constexpr size_t MGX_PARSE_ARGS_BYTES = 144;            // sizeof(RpChunk), reads_parse.hpp
 constexpr size_t MGX_MAPFMT_ARGS_BYTES = 120;           // sizeof(MfBatch), map_format.hpp
+constexpr size_t MGX_JSONFMT_ARGS_BYTES = 120;          // sizeof(JfBatch), json_format.hpp
 
 struct mgx_annotation;
 
@@ -83,6 +84,12 @@ int mgx_launch_format_patch(uint64_t *line_len, const uint32_t *queries, const u
 // every query; write: the text at text + line_begin[q].
 int mgx_launch_mapfmt_size(const void *args, void *stream);
 int mgx_launch_mapfmt_write(const void *args, void *stream);
+
+// mgx_jsonfmt.hip: the text of `align --json` for a range of a batch (json_format.hpp).  args: a JfBatch (host memory).  size:
+// line_len[i] for every query of the range, and its capacity-status queries into cap_list / cap_count; write: the lines at
+// text + line_begin[i].  (The lengths of host-formatted lines are patched in by mgx_launch_format_patch.)
+int mgx_launch_jsonfmt_size(const void *args, void *stream);
+int mgx_launch_jsonfmt_write(const void *args, void *stream);
 
 // mgx_parse.hip: FASTA / FASTQ text to read batches (reads_parse.hpp).  args: an RpChunk (host memory).  count: the '\n' mask and
 // count of every 64-byte span; table: line_begin[] from the masks and the scanned counts; classify: what every line adds (items);

@@ -28,6 +28,7 @@
 #include "kernel_units.hpp"
 #include "tsv_format.hpp"
 #include "map_format.hpp"
+#include "json_format.hpp"
 
 using namespace mgx;
 static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES && sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES
@@ -2569,6 +2570,142 @@ size_t mgx_format_json(const mgx_results *res, uint64_t qi, const char *header, 
         buf[nc] = 0;
     }
     return s.size();
+}
+
+// ---- the `align --json` text of a range of a batch, written by kernels (json_format.hpp, mgx_jsonfmt.hip) --------
+enum { JF_CNT_SIZE = 0, JF_CNT_WRITE, JF_CNT_HOST_QUERIES, JF_CNT_D2H_BYTES };
+static std::atomic<uint64_t> g_jsonfmt_counts[4];       // mgx_format_json_kernel_launch_counts
+void mgx_format_json_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_jsonfmt_counts[x].load(); }
+
+int mgx_format_json_batch(mgx_aligner *A, const char *headers, const uint64_t *header_offsets, uint64_t first, uint64_t n, mgx_text *out) {
+    static_assert(sizeof(JfBatch) == MGX_JSONFMT_ARGS_BYTES, "JfBatch differs from what mgx_jsonfmt.hip takes");
+    if (!A || !out || (n && (!headers || !header_offsets))) return fail(MGX_ERR_INVALID, "mgx_format_json_batch: null argument");
+    if (A->cfg.post_chain_alignments)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_format_json_batch: post_chain_alignments is set and JSON output for chains is not supported");
+    const uint64_t n_batch = A->n_reads;
+    if (first > n_batch || n > n_batch - first)
+        return fail(MGX_ERR_INVALID, "mgx_format_json_batch: queries %llu .. %llu are beyond the staged batch of %llu", (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)n_batch);
+    A->h_line_begin.assign(n + 1, 0);
+    out->n_queries = n; out->text = A->h_text ? A->h_text : ""; out->line_begin = A->h_line_begin.data();
+    if (!n) return MGX_OK;
+    if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
+    if (!(A->aligned_generation == A->stage_generation && A->last_d_seqs && A->last_d_offsets))
+        return fail(MGX_ERR_INVALID, "mgx_format_json_batch: no alignment batch staged: mgx_align_batch_device has not run on this handle, or a "
+                                     "map / summary call ran since");
+    if (n >= 0x7FFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_json_batch: more than 2^31 - 2 queries in a range");
+    HIP_TRY(hipSetDevice(A->graph->device));
+    auto d2h = [&](void *dst, const void *src, size_t bytes) {
+        g_jsonfmt_counts[JF_CNT_D2H_BYTES] += bytes;
+        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    // the range's headers and their offsets (as the caller counts them: the kernels subtract the first one)
+    const uint64_t header_from = header_offsets[0], header_bytes = header_offsets[n] - header_from;
+    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
+    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
+    if (int rc = A->tf_cap.ensure((n + 1) * 4)) return rc;
+    if (header_bytes) HIP_TRY(hipMemcpyAsync(A->tf_headers.p, headers + header_from, header_bytes, hipMemcpyHostToDevice, A->hstream));
+    HIP_TRY(hipMemcpyAsync(A->tf_header_offsets.p, header_offsets, (n + 1) * 8, hipMemcpyHostToDevice, A->hstream));
+    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
+    JfBatch b;
+    memset(&b, 0, sizeof(b));
+    b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
+    b.seqs = A->last_d_seqs; b.offsets = A->last_d_offsets;
+    b.headers = A->tf_headers.as<char>(); b.header_from = header_from; b.header_offsets = A->tf_header_offsets.as<uint64_t>();
+    b.line_len = d_len; b.line_begin = d_begin;
+    b.cap_list = A->tf_cap.as<uint32_t>(); b.cap_count = reinterpret_cast<unsigned long long *>(d_begin + n + 1);
+    b.first = first; b.n_queries = n; b.k = A->graph->g.k; b.labeled = A->anno ? 1u : 0u;
+    // pass 1: the lengths (d_len[n] = 0 closes the scan), the capacity-status queries; the scan gives line_begin
+    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
+    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
+    HIP_TRY((hipError_t)mgx_launch_jsonfmt_size(&b, A->hstream));
+    ++g_jsonfmt_counts[JF_CNT_SIZE];
+    auto scan = [&]() -> int {
+        size_t tmp_bytes = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+        if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+        return MGX_OK;
+    };
+    if (int rc = scan()) return rc;
+    uint64_t counters[2] = { 0, 0 };                  // the text's bytes, the capacity-status queries
+    HIP_TRY(d2h(counters, d_begin + n, 16));
+    // the capacity-status queries of the range: aligned again with larger limits, formatted by mgx_format_json, lengths patched in
+    std::vector<uint64_t> todo;
+    std::vector<std::string> host_lines;
+    if (counters[1]) {
+        std::vector<uint32_t> cap(counters[1]);
+        HIP_TRY(d2h(cap.data(), A->tf_cap.p, cap.size() * 4));
+        std::sort(cap.begin(), cap.end());
+        for (uint32_t i : cap) todo.push_back(first + i);
+        if (!A->retry_capacity)
+            return fail(MGX_ERR_CAPACITY, "mgx_format_json_batch: query %llu (and %llu more) has a capacity status and retry_capacity is off",
+                        (unsigned long long)todo.front(), (unsigned long long)todo.size() - 1);
+        std::vector<HostResults> fixed;
+        std::vector<uint8_t> have;
+        std::vector<uint64_t> h_off;
+        std::vector<char> h_seq;
+        if (int rc = realign_capacity_queries(A, A->last_d_seqs, A->last_d_offsets, n_batch, todo, fixed, have, h_off, h_seq)) return rc;
+        g_jsonfmt_counts[JF_CNT_D2H_BYTES] += (n_batch + 1) * 8 + (h_seq.size() - 1);
+        std::vector<uint64_t> patch_len(todo.size());
+        host_lines.resize(todo.size());
+        for (size_t t = 0; t < todo.size(); ++t) {
+            const uint64_t q = todo[t];
+            if (!have[t])
+                return fail(MGX_ERR_CAPACITY, "mgx_format_json_batch: query %llu keeps its capacity status after the retry", (unsigned long long)q);
+            mgx_results v;
+            fixed[t].view(&v);
+            const std::string header(headers + header_offsets[q - first], headers + header_offsets[q - first + 1]);
+            const char *query = h_seq.data() + (h_off[q] - h_off[todo.front()]);
+            const size_t qlen = h_off[q + 1] - h_off[q];
+            std::string &line = host_lines[t];
+            line.resize(mgx_format_json(&v, 0, header.c_str(), query, qlen, b.k, nullptr, 0) + 1);
+            mgx_format_json(&v, 0, header.c_str(), query, qlen, b.k, &line[0], line.size());
+            line.pop_back();                         // (the formatter's NUL)
+            patch_len[t] = line.size();
+        }
+        A->hstats.n_capacity_retried = todo.size();
+        g_jsonfmt_counts[JF_CNT_HOST_QUERIES] += todo.size();
+        // (i, length) pairs: the i as 4-byte words behind the 8-byte lengths
+        if (int rc = A->tf_patch.ensure(todo.size() * 12 + 16)) return rc;
+        uint32_t *d_pq = reinterpret_cast<uint32_t *>(A->tf_patch.as<uint64_t>() + todo.size());
+        HIP_TRY(hipMemcpyAsync(A->tf_patch.p, patch_len.data(), todo.size() * 8, hipMemcpyHostToDevice, A->hstream));
+        HIP_TRY(hipMemcpyAsync(d_pq, cap.data(), todo.size() * 4, hipMemcpyHostToDevice, A->hstream));
+        HIP_TRY((hipError_t)mgx_launch_format_patch(d_len, d_pq, A->tf_patch.as<uint64_t>(), (uint32_t)todo.size(), A->hstream));
+        if (int rc = scan()) return rc;
+        HIP_TRY(d2h(counters, d_begin + n, 8));
+        HIP_TRY(hipStreamSynchronize(A->hstream));   // (patch_len and cap are read by the copies above)
+    }
+    // pass 2: the text
+    const uint64_t text_bytes = counters[0];
+    if (A->tf_text.ensure(text_bytes + 16) != MGX_OK)
+        return fail(MGX_ERR_OOM, "mgx_format_json_batch: the text of queries %llu .. %llu needs %llu bytes and no device buffer of that size "
+                                 "could be allocated: take a smaller range", (unsigned long long)first, (unsigned long long)(first + n),
+                    (unsigned long long)text_bytes);
+    if (text_bytes + 1 > A->h_text_bytes) {
+        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
+        const size_t want = text_bytes + text_bytes / 8 + 4096;
+        void *p = nullptr;
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            out->text = "";
+            return fail(MGX_ERR_OOM, "mgx_format_json_batch: the text of queries %llu .. %llu needs %llu bytes and no pinned host buffer of "
+                                     "that size could be allocated: take a smaller range", (unsigned long long)first,
+                        (unsigned long long)(first + n), (unsigned long long)text_bytes);
+        }
+        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
+    }
+    b.text = A->tf_text.as<char>();
+    HIP_TRY((hipError_t)mgx_launch_jsonfmt_write(&b, A->hstream));
+    ++g_jsonfmt_counts[JF_CNT_WRITE];
+    g_jsonfmt_counts[JF_CNT_D2H_BYTES] += text_bytes;
+    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
+    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
+    for (size_t t = 0; t < todo.size(); ++t) memcpy(A->h_text + A->h_line_begin[todo[t] - first], host_lines[t].data(), host_lines[t].size());
+    out->text = A->h_text;
+    return MGX_OK;
 }
 
 } // extern "C"

@@ -90,16 +90,17 @@ MGX_DEV TfAln tf_aln_header(const TfBatch &b, const ReadResult &r, int32_t a, ui
     return h;
 }
 
+// (the fields the formatters read; the record's tail is parity-test material)
 template <bool U>
-MGX_DEV ReadResult tf_record(const TfBatch &b, uint64_t q) {
-    // (the fields the formatter reads; the record's tail is parity-test material)
-    const ReadResult *p = b.results + q;
+MGX_DEV ReadResult tf_record_at(const ReadResult *p) {
     ReadResult r;
     r.status = tf_ld<U>(&p->status); r.n_alignments = tf_ld<U>(&p->n_alignments); r.score = tf_ld<U>(&p->score);
     r.offset = tf_ld<U>(&p->offset); r.n_nodes = tf_ld<U>(&p->n_nodes); r.n_cigar = tf_ld<U>(&p->n_cigar);
     r.seq_len = tf_ld<U>(&p->seq_len); r.orientation = tf_ld<U>(&p->orientation); r.stream_off = tf_ld<U>(&p->stream_off);
     return r;
 }
+template <bool U>
+MGX_DEV ReadResult tf_record(const TfBatch &b, uint64_t q) { return tf_record_at<U>(b.results + q); }
 
 MGX_DEV bool tf_has_alignments(const ReadResult &r) { return r.status == ST_OK && r.n_alignments > 0; }
 

@@ -388,6 +388,26 @@ class HipDBGAligner : public IDBGAligner {
         if (text.n_queries != n) throw std::runtime_error("mgx_format_tsv_batch: the handle's batch is not this one");
         return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
     }
+    // The `align --json` lines of queries first .. first + n of the batch align_batch_device ran last, written on the device
+    // (mgx_format_json_batch): what mgx_format_json gives for those queries, in query order.  JSON text is large (about 60 bytes
+    // per path node), so a caller formats a batch in slices: the slices' texts concatenated are the batch's.  The view is the
+    // handle's and stays valid until its next batch or format call.  Throws for post_chain_alignments (the reference has no JSON
+    // for chains) and for capacity statuses no retry cures.
+    std::string_view format_batch_json(const std::vector<Query> &seq_batch, uint64_t first, uint64_t n) const {
+        if (first > seq_batch.size() || n > seq_batch.size() - first) throw std::runtime_error("format_batch_json: the range is beyond the batch");
+        std::string headers;
+        std::vector<uint64_t> offsets(n + 1, 0);
+        for (uint64_t t = 0; t < n; ++t) {
+            headers += seq_batch[first + t].first;
+            offsets[t + 1] = headers.size();
+        }
+        if (headers.empty()) headers.push_back('\0');               // (a range of empty headers still needs a pointer)
+        return format_json_range(headers.data(), offsets.data(), first, n);
+    }
+    // ... with the names as flat arrays (mgx_reads::names / name_offsets; `name_offsets` points at the BATCH's first record)
+    std::string_view format_batch_json(const char *names, const uint64_t *name_offsets, uint64_t first, uint64_t n) const {
+        return format_json_range(names, name_offsets + first, first, n);
+    }
     mgx_aligner *handle() const { return a_; }
     static void deliver(const mgx_results &res, const std::vector<Query> &seq_batch, const AlignmentCallback &callback) {
         std::vector<AlignmentResults> results;
@@ -422,6 +442,12 @@ class HipDBGAligner : public IDBGAligner {
     // the reference builds one aligner per thread-pool task (cli/align.cpp:440-475): every handle works on a stream of its own, so
     // that the tasks of one device overlap instead of taking turns on the default stream (batches arrive from host memory: nothing
     // of the caller's is ordered against it)
+    std::string_view format_json_range(const char *headers, const uint64_t *header_offsets, uint64_t first, uint64_t n) const {
+        mgx_text text{};
+        if (int rc = mgx_format_json_batch(a_, headers, header_offsets, first, n, &text))
+            throw std::runtime_error(std::string("mgx_format_json_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+    }
     void own_stream() {
         if (getenv("MGX_ADAPTER_DEFAULT_STREAM")) return;          // (A/B switch: every handle on the legacy default stream, as before round 6)
         if (int rc = mgx_aligner_create_stream(a_)) {

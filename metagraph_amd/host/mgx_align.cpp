@@ -20,6 +20,17 @@
 //                             and mgx_format_map cut a name at its first NUL)
 //             [--format-on-device]  the TSV text of every batch is written by kernels (mgx_format_tsv_batch) and printed with one write
 //                             per batch, instead of one host-built string per query; same bytes.  Not with --map or --rccl-gather
+//             [--json]        the lines of `metagraph align --json` (cli/align.cpp:287-305) instead of TSV: one JSON object per
+//                             alignment, a {"name":..,"sequence":""} object for a query without one; input order with -p 1.  Without
+//                             --format-on-device: mgx_fetch_results and mgx_format_json per query.  With --format-on-device: written by
+//                             kernels (mgx_format_json_batch), a batch in slices, one write per slice; with --parse-on-device in
+//                             addition as for TSV.  Same bytes in every form.  Labels are not printed (JSON carries none).  Not with
+//                             --map or --rccl-gather, nor with post_chain_alignments (the reference has no JSON for chains)
+//             [--json-slice-bytes N]  with --json --format-on-device: JSON text is ~100 bytes per query character (one mapping object per
+//                             path node), so a batch is formatted in slices: consecutive queries are added to a slice while its
+//                             ESTIMATED text — (128 bytes per character + twice the header + 512) x num_alternative_paths per
+//                             query — stays within N (default 268435456; a slice always takes at least one query).  The estimate is
+//                             an upper bound for reads without long insertions or many escaped bytes; the output does not depend on N
 //             [--parse-on-device]  with --format-on-device, -p 1 and --devices 1: the file is read in large chunks with read(2) into
 //                             a pinned buffer and parsed by kernels (mgx_parse_reads) — file bytes in, TSV bytes out, no per-read
 //                             host work.  Files inside the parser's grammar print the same bytes, with two exceptions
@@ -127,6 +138,8 @@ int main(int argc, char **argv) {
     bool have_lim = false;
     int devices = 1;
     bool rccl_gather = false, format_on_device = false, parse_on_device = false, map_on_device = false;
+    bool json = false, have_json_slice_bytes = false;
+    uint64_t json_slice_bytes = 256ull << 20;          // --json-slice-bytes N: the estimated text of one mgx_format_json_batch call
     uint64_t parse_chunk_bytes = 256ull << 20;         // --parse-chunk-bytes N (test hook: several chunks from a small file)
     std::vector<const char *> anno_paths;
     std::vector<std::string> kernel_options;            // --kernel-option key=value: result-preserving kernel selection (A/B runs)
@@ -154,6 +167,8 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rccl-gather")) rccl_gather = true;
         else if (!strcmp(argv[i], "--format-on-device")) format_on_device = true;
         else if (!strcmp(argv[i], "--parse-on-device")) parse_on_device = true;
+        else if (!strcmp(argv[i], "--json")) json = true;
+        else if (!strcmp(argv[i], "--json-slice-bytes") && i + 1 < argc) { json_slice_bytes = std::max<uint64_t>(1, strtoull(argv[++i], nullptr, 10)); have_json_slice_bytes = true; }
         else if (!strcmp(argv[i], "--map-on-device")) map_on_device = true;
         else if (!strcmp(argv[i], "--parse-chunk-bytes") && i + 1 < argc) parse_chunk_bytes = std::max<uint64_t>(1, strtoull(argv[++i], nullptr, 10));
         else if (!strcmp(argv[i], "--time")) report_time = true;            // wall time of the align loop (batches -> results printed) on stderr
@@ -181,6 +196,26 @@ int main(int argc, char **argv) {
         fprintf(stderr, "error: --format-on-device formats the alignment TSV of a batch on its own device: not with %s\n", map_mode ? "--map" : "--rccl-gather");
         return 1;
     }
+    if (json && (map_mode || rccl_gather || cfg.post_chain_alignments)) {
+        fprintf(stderr, "error: --json prints the alignments of a batch from its own device: not with %s\n",
+                map_mode ? "--map" : rccl_gather ? "--rccl-gather" : "post_chain_alignments (the reference has no JSON output for chains)");
+        return 1;
+    }
+    if (have_json_slice_bytes && !(json && format_on_device)) {
+        fprintf(stderr, "error: --json-slice-bytes bounds the text of one mgx_format_json_batch call: it needs --json --format-on-device\n");
+        return 1;
+    }
+    // the end of the --json slice that starts at query `first` of a batch of n: see --json-slice-bytes
+    const uint64_t json_paths = std::max<uint64_t>(1, cfg.num_alternative_paths);
+    auto json_slice_end = [&](uint64_t first, uint64_t n, auto &&query_len, auto &&header_len) {
+        uint64_t end = first, estimate = 0;
+        while (end < n) {
+            estimate += (128 * (uint64_t)query_len(end) + 2 * (uint64_t)header_len(end) + 512) * json_paths;
+            if (end > first && estimate > json_slice_bytes) break;
+            ++end;
+        }
+        return end;
+    };
     if (map_mode) anno_paths.clear();                    // no annotation is loaded in this mode (cli/align.cpp:316-318)
     try {
         // one replica of the index per device (3.5 B/edge + the suffix-range table each); more devices than the box shows is an
@@ -303,6 +338,17 @@ int main(int argc, char **argv) {
                         : new HipDBGAligner(graph, cfg, have_lim ? &lim : nullptr));
                     for (const std::string &opt : kernel_options) aligner_p->set_kernel_option(opt);
                     aligner_p->align_batch_device(d_seqs, d_offsets, i - first);
+                    if (json) {
+                        const uint64_t nb = i - first, *ho = r.host_offsets + first, *no = r.name_offsets + first;
+                        for (uint64_t at = 0; at < nb;) {
+                            const uint64_t end = json_slice_end(at, nb, [&](uint64_t t) { return ho[t + 1] - ho[t]; }, [&](uint64_t t) { return no[t + 1] - no[t]; });
+                            const std::string_view text = aligner_p->format_batch_json(r.names, no, at, end - at);
+                            std::cout.write(text.data(), (std::streamsize)text.size());
+                            at = end;
+                        }
+                        ++n_batches;
+                        continue;
+                    }
                     const std::string_view text = aligner_p->format_batch_tsv(r.names, r.name_offsets + first, i - first, annotation ? &label_names : nullptr);
                     std::cout.write(text.data(), (std::streamsize)text.size());
                     ++n_batches;
@@ -399,6 +445,34 @@ int main(int argc, char **argv) {
                     // (the workers of one device share it: every handle on its own stream, its arenas sized for its share)
                     aligner.set_device_share((threads + (unsigned)devices - 1) / (unsigned)devices);
                     for (const std::string &opt : kernel_options) aligner.set_kernel_option(opt);
+                    if (json) {
+                        const std::vector<IDBGAligner::Query> &batch = batches[bi];
+                        aligner.align_batch_device(batch);
+                        std::lock_guard<std::mutex> lock(print_mutex);          // (a batch's lines stay together)
+                        if (format_on_device) {
+                            for (uint64_t at = 0; at < batch.size();) {
+                                const uint64_t end = json_slice_end(at, batch.size(), [&](uint64_t t) { return batch[t].second.size(); },
+                                                                    [&](uint64_t t) { return batch[t].first.size(); });
+                                const std::string_view text = aligner.format_batch_json(batch, at, end - at);
+                                std::cout.write(text.data(), (std::streamsize)text.size());
+                                at = end;
+                            }
+                            continue;
+                        }
+                        mgx_results res{};
+                        if (int rc = mgx_fetch_results(aligner.handle(), &res))
+                            throw std::runtime_error(std::string("mgx_fetch_results: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+                        std::string line;
+                        for (size_t t = 0; t < batch.size(); ++t) {
+                            if (res.status[t] != MGX_OK)
+                                throw std::runtime_error("query " + std::to_string(t) + " (" + batch[t].first + "): status " + std::to_string(res.status[t]));
+                            const size_t need = mgx_format_json(&res, t, batch[t].first.c_str(), batch[t].second.data(), batch[t].second.size(), k, nullptr, 0);
+                            line.resize(need + 1);
+                            mgx_format_json(&res, t, batch[t].first.c_str(), batch[t].second.data(), batch[t].second.size(), k, line.data(), need + 1);
+                            std::cout.write(line.data(), (std::streamsize)need);
+                        }
+                        continue;
+                    }
                     if (format_on_device) {
                         aligner.align_batch_device(batches[bi]);
                         const std::string_view text = aligner.format_batch_tsv(batches[bi], annotation ? &label_names : nullptr);
