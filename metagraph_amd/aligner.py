@@ -270,10 +270,7 @@ class Aligner:
         blob, hoff, n_headers = _pack_headers(headers)
         t = capi.Text()
         _check(capi.lib().mgx_format_map_batch(self.h, blob, hoff.ctypes.data, fmt, discovery_fraction, C.byref(t)))
-        if t.n_queries != n_headers:
-            raise ValueError("format_map_batch: %d headers for a batch of %d queries" % (n_headers, t.n_queries))
-        lb = np.ctypeslib.as_array(t.line_begin, shape=(n_headers + 1,)).copy()
-        return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+        return _text_of(t, n_headers, "format_map_batch: %d headers for a batch of %d queries")
 
     def set_pipeline(self, name):
         """Kernel selection: 'split8' (the name of the one pipeline: accepted, selects nothing), 'general' / 'chain'
@@ -320,8 +317,7 @@ class Aligner:
             raise ValueError("format_json_batch: %d headers for a range of %d queries" % (n_headers, n))
         t = capi.Text()
         _check(capi.lib().mgx_format_json_batch(self.h, blob, hoff.ctypes.data, first, n, C.byref(t)))
-        lb = np.ctypeslib.as_array(t.line_begin, shape=(n + 1,)).copy()
-        return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+        return _text_of(t, n, "format_json_batch: %d headers for a range of %d queries")
 
     def format_tsv_batch(self, headers, label_names=None):
         """mgx_format_tsv_batch: the TSV text of the batch align_device / align_batch ran last, written by kernels.
@@ -332,10 +328,16 @@ class Aligner:
         arr = (C.c_char_p * len(names))(*names) if names else None
         t = capi.Text()
         _check(capi.lib().mgx_format_tsv_batch(self.h, blob, hoff.ctypes.data, arr, len(names), C.byref(t)))
-        if t.n_queries != n_headers:
-            raise ValueError("format_tsv_batch: %d headers for a batch of %d queries" % (n_headers, t.n_queries))
-        lb = np.ctypeslib.as_array(t.line_begin, shape=(n_headers + 1,)).copy()
-        return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
+        return _text_of(t, n_headers, "format_tsv_batch: %d headers for a batch of %d queries")
+
+
+def _text_of(t, n_headers, mismatch):
+    """the shared tail of the format_*_batch methods: the header count against the mgx_text's n_queries (mismatch: the message of
+    the ValueError), then -> (bytes of the text, numpy uint64 copy of its n_headers + 1 offsets)"""
+    if t.n_queries != n_headers:
+        raise ValueError(mismatch % (n_headers, t.n_queries))
+    lb = np.ctypeslib.as_array(t.line_begin, shape=(n_headers + 1,)).copy()
+    return (C.string_at(t.text, int(lb[-1])) if int(lb[-1]) else b""), lb
 
 
 def _pack_headers(headers):
@@ -417,36 +419,34 @@ class ReadParser:
         return ParsedReads(self, r)
 
 
+def _four_counts(fn):
+    out = (C.c_uint64 * 4)()
+    fn(out)
+    return tuple(int(x) for x in out)
+
+
 def parse_kernel_launch_counts():
     """mgx_parse_kernel_launch_counts -> (line-pass kernel launches, copy-pass kernel launches, bytes host-to-device, bytes
     device-to-host) since the library was loaded"""
-    out = (C.c_uint64 * 4)()
-    capi.lib().mgx_parse_kernel_launch_counts(out)
-    return tuple(int(x) for x in out)
+    return _four_counts(capi.lib().mgx_parse_kernel_launch_counts)
 
 
 def format_kernel_launch_counts():
     """mgx_format_kernel_launch_counts -> (size kernel launches, write kernel launches, host-formatted lines, bytes copied
     device-to-host by format_tsv_batch) since the library was loaded"""
-    out = (C.c_uint64 * 4)()
-    capi.lib().mgx_format_kernel_launch_counts(out)
-    return tuple(int(x) for x in out)
+    return _four_counts(capi.lib().mgx_format_kernel_launch_counts)
 
 
 def format_json_kernel_launch_counts():
     """mgx_format_json_kernel_launch_counts -> (size kernel launches, write kernel launches, queries formatted on the host, bytes
     copied device-to-host by format_json_batch) since the library was loaded"""
-    out = (C.c_uint64 * 4)()
-    capi.lib().mgx_format_json_kernel_launch_counts(out)
-    return tuple(int(x) for x in out)
+    return _four_counts(capi.lib().mgx_format_json_kernel_launch_counts)
 
 
 def format_map_kernel_launch_counts():
     """mgx_format_map_kernel_launch_counts -> (size kernel launches, write kernel launches, bytes copied device-to-host, bytes
     copied host-to-device by format_map_batch) since the library was loaded"""
-    out = (C.c_uint64 * 4)()
-    capi.lib().mgx_format_map_kernel_launch_counts(out)
-    return tuple(int(x) for x in out)
+    return _four_counts(capi.lib().mgx_format_map_kernel_launch_counts)
 
 
 def map_present(counts, query_len, k, map_length=0, discovery_fraction=0.7):

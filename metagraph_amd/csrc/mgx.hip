@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -2185,7 +2186,143 @@ size_t mgx_format_tsv_labeled(const mgx_results *res, uint64_t qi, const char *h
     return s.size();
 }
 
-// ---- the TSV text of a batch, written by kernels (tsv_format.hpp, mgx_format.hip) --------------------------
+// ---- the text of a batch, written by kernels: the one host sequence behind mgx_format_tsv_batch, mgx_format_map_batch and
+// mgx_format_json_batch.  An entry point checks its arguments and describes its job; format_on_device runs it.
+struct FormatJob {
+    const char *fn;                                  // the entry point's name, for messages
+    const char *oom_advice;                          // the end of the two out-of-memory messages ("" or what the caller can do)
+    std::atomic<uint64_t> *size_launches, *write_launches, *d2h_bytes, *h2d_bytes, *host_lines;    // its counters; null: it has none
+    int (*launch_size)(const void *, void *);        // the two kernels' launchers ...
+    int (*launch_write)(const void *, void *);
+    const void *params;                              // ... their TfBatch / MfBatch / JfBatch ...
+    char **text;                                     // ... and its `text` field (set here, once the size of the text is known)
+    const char *headers;                             // header i of the range: headers[header_offsets[i] .. header_offsets[i + 1])
+    const uint64_t *header_offsets;
+    uint64_t header_from;                            // header_offsets[0] as the kernels see it: the uploaded bytes start there
+    uint64_t first, n, n_batch;                      // queries first .. first + n of the staged batch of n_batch
+    // Called once tf_headers, tf_header_offsets, tf_len, tf_begin (and tf_cap, with host_line) are large enough and the headers are
+    // on the stream: fills *params but for `text`, uploads the entry point's own tables.
+    std::function<int()> bind;
+    // The text of a query that the host aligned again: (view of that query's results alone, header, query bytes, their count).
+    // None: the formatter leaves no query to the host; no tf_cap, no retry.
+    std::function<std::string(const mgx_results &, const char *, const char *, size_t)> host_line;
+};
+
+// what a per-query host formatter writes, as a string: size the line, fill it, drop the formatter's NUL
+static std::string host_formatted(const std::function<size_t(char *, size_t)> &format) {
+    std::string line(format(nullptr, 0) + 1, '\0');
+    format(&line[0], line.size());
+    line.pop_back();
+    return line;
+}
+
+static int format_on_device(mgx_aligner *A, const FormatJob &job, mgx_text *out) {
+    const uint64_t first = job.first, n = job.n;
+    auto count = [](std::atomic<uint64_t> *c, uint64_t by) { if (c) *c += by; };
+    auto d2h = [&](void *dst, const void *src, size_t bytes) {
+        count(job.d2h_bytes, bytes);
+        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    auto h2d = [&](void *dst, const void *src, size_t bytes) {
+        count(job.h2d_bytes, bytes);
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, A->hstream);
+    };
+    // the range's headers and their offsets (as the caller counts them: uploaded with every call)
+    const uint64_t header_bytes = job.header_offsets[n] - job.header_from;
+    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
+    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
+    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
+    if (job.host_line) if (int rc = A->tf_cap.ensure((n + 1) * 4)) return rc;
+    if (header_bytes) HIP_TRY(h2d(A->tf_headers.p, job.headers + job.header_from, header_bytes));
+    HIP_TRY(h2d(A->tf_header_offsets.p, job.header_offsets, (n + 1) * 8));
+    if (int rc = job.bind()) return rc;
+    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
+    // pass 1: the line lengths (d_len[n] = 0 closes the scan), the capacity-status queries; the scan gives line_begin
+    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
+    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
+    HIP_TRY((hipError_t)job.launch_size(job.params, A->hstream));
+    count(job.size_launches, 1);
+    auto scan = [&]() -> int {
+        size_t tmp_bytes = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+        if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+        return MGX_OK;
+    };
+    if (int rc = scan()) return rc;
+    uint64_t counters[2] = { 0, 0 };                  // the text's bytes, the capacity-status queries (0 without host_line)
+    HIP_TRY(d2h(counters, d_begin + n, 16));
+    // the capacity-status queries of the range: aligned again with larger limits, formatted by host_line, their lengths patched in
+    std::vector<uint64_t> todo;
+    std::vector<std::string> host_lines;
+    if (job.host_line && counters[1]) {
+        std::vector<uint32_t> cap(counters[1]);
+        HIP_TRY(d2h(cap.data(), A->tf_cap.p, cap.size() * 4));
+        std::sort(cap.begin(), cap.end());
+        for (uint32_t i : cap) todo.push_back(first + i);
+        if (!A->retry_capacity)
+            return fail(MGX_ERR_CAPACITY, "%s: query %llu (and %llu more) has a capacity status and retry_capacity is off", job.fn,
+                        (unsigned long long)todo.front(), (unsigned long long)todo.size() - 1);
+        std::vector<HostResults> fixed;
+        std::vector<uint8_t> have;
+        std::vector<uint64_t> h_off;
+        std::vector<char> h_seq;
+        if (int rc = realign_capacity_queries(A, A->last_d_seqs, A->last_d_offsets, job.n_batch, todo, fixed, have, h_off, h_seq)) return rc;
+        count(job.d2h_bytes, (job.n_batch + 1) * 8 + (h_seq.size() - 1));
+        std::vector<uint64_t> patch_len(todo.size());
+        host_lines.resize(todo.size());
+        for (size_t t = 0; t < todo.size(); ++t) {
+            const uint64_t q = todo[t];
+            if (!have[t]) return fail(MGX_ERR_CAPACITY, "%s: query %llu keeps its capacity status after the retry", job.fn, (unsigned long long)q);
+            mgx_results v;
+            fixed[t].view(&v);
+            const std::string header(job.headers + job.header_offsets[q - first], job.headers + job.header_offsets[q - first + 1]);
+            host_lines[t] = job.host_line(v, header.c_str(), h_seq.data() + (h_off[q] - h_off[todo.front()]), h_off[q + 1] - h_off[q]);
+            patch_len[t] = host_lines[t].size();
+        }
+        A->hstats.n_capacity_retried = todo.size();
+        count(job.host_lines, todo.size());
+        // (i, length) pairs: the i as 4-byte words behind the 8-byte lengths
+        if (int rc = A->tf_patch.ensure(todo.size() * 12 + 16)) return rc;
+        uint32_t *d_pq = reinterpret_cast<uint32_t *>(A->tf_patch.as<uint64_t>() + todo.size());
+        HIP_TRY(h2d(A->tf_patch.p, patch_len.data(), todo.size() * 8));
+        HIP_TRY(h2d(d_pq, cap.data(), todo.size() * 4));
+        HIP_TRY((hipError_t)mgx_launch_format_patch(d_len, d_pq, A->tf_patch.as<uint64_t>(), (uint32_t)todo.size(), A->hstream));
+        if (int rc = scan()) return rc;
+        HIP_TRY(d2h(counters, d_begin + n, 8));
+        HIP_TRY(hipStreamSynchronize(A->hstream));   // (patch_len and cap are read by the copies above)
+    }
+    // pass 2: the text
+    const uint64_t text_bytes = counters[0];
+    auto no_buffer = [&](const char *which) {
+        return fail(MGX_ERR_OOM, "%s: the text of queries %llu .. %llu needs %llu bytes and no %s buffer of that size could be allocated%s", job.fn,
+                    (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)text_bytes, which, job.oom_advice);
+    };
+    if (A->tf_text.ensure(text_bytes + 16) != MGX_OK) return no_buffer("device");
+    if (text_bytes + 1 > A->h_text_bytes) {
+        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
+        const size_t want = text_bytes + text_bytes / 8 + 4096;
+        void *p = nullptr;
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            out->text = "";                          // (what it pointed at is freed)
+            return no_buffer("pinned host");
+        }
+        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
+    }
+    *job.text = A->tf_text.as<char>();
+    HIP_TRY((hipError_t)job.launch_write(job.params, A->hstream));
+    count(job.write_launches, 1);
+    count(job.d2h_bytes, text_bytes);
+    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
+    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
+    for (size_t t = 0; t < todo.size(); ++t) memcpy(A->h_text + A->h_line_begin[todo[t] - first], host_lines[t].data(), host_lines[t].size());
+    out->text = A->h_text;
+    return MGX_OK;
+}
+
+// ---- the TSV text of a batch (tsv_format.hpp, mgx_format.hip) ------------------------------------------------------------
 enum { TF_CNT_SIZE = 0, TF_CNT_WRITE, TF_CNT_HOST_LINES, TF_CNT_D2H_BYTES };
 static std::atomic<uint64_t> g_format_counts[4];        // mgx_format_kernel_launch_counts
 void mgx_format_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_format_counts[x].load(); }
@@ -2205,126 +2342,51 @@ int mgx_format_tsv_batch(mgx_aligner *A, const char *headers, const uint64_t *he
     if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
     if (!(A->aligned_generation == A->stage_generation && A->last_d_seqs && A->last_d_offsets))
         return fail(MGX_ERR_INVALID, "mgx_format_tsv_batch: no aligned batch on this handle, or another batch was staged after mgx_align_batch_device");
-    if (n >= 0xFFFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_tsv_batch: more than 2^32 - 2 queries in a batch");
+    if (n >= 0x7FFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_tsv_batch: more than 2^31 - 2 queries in a batch");
     HIP_TRY(hipSetDevice(A->graph->device));
-    auto d2h = [&](void *dst, const void *src, size_t bytes) {
-        g_format_counts[TF_CNT_D2H_BYTES] += bytes;
-        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
-    };
-    // inputs of the caller: headers, their offsets, the label names (uploaded with every call: a few hundred bytes)
-    const uint64_t header_bytes = header_offsets[n];
+    // the label names (uploaded with every call: a few hundred bytes): for the kernels a blob, for the host formatter C strings
     std::string name_blob;
     std::vector<uint32_t> name_begin(1, 0);
-    for (uint32_t j = 0; j < n_label_names; ++j) { name_blob += label_names[j] ? label_names[j] : ""; name_begin.push_back((uint32_t)name_blob.size()); }
-    const size_t names_at = (name_blob.size() + 3) & ~(size_t)3;                 // the begins follow the bytes, 4-byte aligned
-    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
-    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
-    if (int rc = A->tf_names.ensure(names_at + name_begin.size() * 4 + 16)) return rc;
-    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
-    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
-    if (int rc = A->tf_cap.ensure((n + 1) * 4)) return rc;
-    if (header_bytes) HIP_TRY(hipMemcpyAsync(A->tf_headers.p, headers, header_bytes, hipMemcpyHostToDevice, A->hstream));
-    HIP_TRY(hipMemcpyAsync(A->tf_header_offsets.p, header_offsets, (n + 1) * 8, hipMemcpyHostToDevice, A->hstream));
-    if (n_label_names) {
-        if (!name_blob.empty()) HIP_TRY(hipMemcpyAsync(A->tf_names.p, name_blob.data(), name_blob.size(), hipMemcpyHostToDevice, A->hstream));
-        HIP_TRY(hipMemcpyAsync(A->tf_names.as<char>() + names_at, name_begin.data(), name_begin.size() * 4, hipMemcpyHostToDevice, A->hstream));
+    std::vector<const char *> names(n_label_names);
+    for (uint32_t j = 0; j < n_label_names; ++j) {
+        names[j] = label_names[j] ? label_names[j] : "";
+        name_blob += names[j];
+        name_begin.push_back((uint32_t)name_blob.size());
     }
-    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
+    const size_t names_at = (name_blob.size() + 3) & ~(size_t)3;                 // the begins follow the bytes, 4-byte aligned
     TfBatch b;
-    memset(&b, 0, sizeof(b));
-    b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
-    b.seqs = A->last_d_seqs; b.offsets = A->last_d_offsets;
-    b.headers = A->tf_headers.as<char>(); b.header_offsets = A->tf_header_offsets.as<uint64_t>();
-    b.name_bytes = A->tf_names.as<char>(); b.name_begin = reinterpret_cast<const uint32_t *>(A->tf_names.as<char>() + names_at);
-    b.line_len = d_len; b.line_begin = d_begin;
-    b.cap_list = A->tf_cap.as<uint32_t>(); b.cap_count = reinterpret_cast<unsigned long long *>(d_begin + n + 1);
-    b.n_queries = n; b.n_names = n_label_names; b.min_path_score = A->cfg.min_path_score; b.labeled = A->anno ? 1u : 0u;
-    // pass 1: the line lengths (d_len[n] = 0 closes the scan), the capacity-status queries; the scan gives line_begin
-    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
-    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
-    HIP_TRY((hipError_t)mgx_launch_format_size(&b, A->hstream));
-    ++g_format_counts[TF_CNT_SIZE];
-    auto scan = [&]() -> int {
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
-        if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+    FormatJob job = {};
+    job.fn = "mgx_format_tsv_batch"; job.oom_advice = "";
+    job.size_launches = &g_format_counts[TF_CNT_SIZE]; job.write_launches = &g_format_counts[TF_CNT_WRITE];
+    job.d2h_bytes = &g_format_counts[TF_CNT_D2H_BYTES]; job.host_lines = &g_format_counts[TF_CNT_HOST_LINES];
+    job.launch_size = mgx_launch_format_size; job.launch_write = mgx_launch_format_write; job.params = &b; job.text = &b.text;
+    job.headers = headers; job.header_offsets = header_offsets;
+    job.n = job.n_batch = n;
+    job.bind = [&]() -> int {
+        if (int rc = A->tf_names.ensure(names_at + name_begin.size() * 4 + 16)) return rc;
+        if (n_label_names) {
+            if (!name_blob.empty()) HIP_TRY(hipMemcpyAsync(A->tf_names.p, name_blob.data(), name_blob.size(), hipMemcpyHostToDevice, A->hstream));
+            HIP_TRY(hipMemcpyAsync(A->tf_names.as<char>() + names_at, name_begin.data(), name_begin.size() * 4, hipMemcpyHostToDevice, A->hstream));
+        }
+        memset(&b, 0, sizeof(b));
+        b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
+        b.seqs = A->last_d_seqs; b.offsets = A->last_d_offsets;
+        b.headers = A->tf_headers.as<char>(); b.header_offsets = A->tf_header_offsets.as<uint64_t>();
+        b.name_bytes = A->tf_names.as<char>(); b.name_begin = reinterpret_cast<const uint32_t *>(A->tf_names.as<char>() + names_at);
+        b.line_len = A->tf_len.as<uint64_t>(); b.line_begin = A->tf_begin.as<uint64_t>();
+        b.cap_list = A->tf_cap.as<uint32_t>(); b.cap_count = reinterpret_cast<unsigned long long *>(A->tf_begin.as<uint64_t>() + n + 1);
+        b.n_queries = n; b.n_names = n_label_names; b.min_path_score = A->cfg.min_path_score; b.labeled = A->anno ? 1u : 0u;
         return MGX_OK;
     };
-    if (int rc = scan()) return rc;
-    uint64_t counters[2] = { 0, 0 };                  // the text's bytes, the capacity-status queries
-    HIP_TRY(d2h(counters, d_begin + n, 16));
-    // the capacity-status queries: aligned again with larger limits, formatted by the host formatter, their lengths patched in
-    std::vector<uint64_t> todo;
-    std::vector<std::string> host_lines;
-    if (counters[1]) {
-        std::vector<uint32_t> cap(counters[1]);
-        HIP_TRY(d2h(cap.data(), A->tf_cap.p, cap.size() * 4));
-        todo.assign(cap.begin(), cap.end());
-        std::sort(todo.begin(), todo.end());
-        if (!A->retry_capacity)
-            return fail(MGX_ERR_CAPACITY, "mgx_format_tsv_batch: query %llu (and %llu more) has a capacity status and retry_capacity is off",
-                        (unsigned long long)todo.front(), (unsigned long long)todo.size() - 1);
-        std::vector<HostResults> fixed;
-        std::vector<uint8_t> have;
-        std::vector<uint64_t> h_off;
-        std::vector<char> h_seq;
-        if (int rc = realign_capacity_queries(A, A->last_d_seqs, A->last_d_offsets, n, todo, fixed, have, h_off, h_seq)) return rc;
-        g_format_counts[TF_CNT_D2H_BYTES] += (n + 1) * 8 + (h_seq.size() - 1);
-        std::vector<const char *> names(label_names, label_names + n_label_names);
-        for (auto &nm : names) if (!nm) nm = "";
-        std::vector<uint64_t> patch_len(todo.size());
-        host_lines.resize(todo.size());
-        for (size_t t = 0; t < todo.size(); ++t) {
-            const uint64_t q = todo[t];
-            if (!have[t])
-                return fail(MGX_ERR_CAPACITY, "mgx_format_tsv_batch: query %llu keeps its capacity status after the retry", (unsigned long long)q);
-            mgx_results v;
-            fixed[t].view(&v);
-            const std::string header(headers + header_offsets[q], headers + header_offsets[q + 1]);
-            const char *query = h_seq.data() + (h_off[q] - h_off[todo.front()]);
-            const size_t qlen = h_off[q + 1] - h_off[q];
-            std::string &line = host_lines[t];
-            line.resize(mgx_format_tsv_labeled(&v, 0, header.c_str(), query, qlen, A->cfg.min_path_score, names.data(), n_label_names, nullptr, 0) + 1);
-            mgx_format_tsv_labeled(&v, 0, header.c_str(), query, qlen, A->cfg.min_path_score, names.data(), n_label_names, &line[0], line.size());
-            line.pop_back();                         // (the formatter's NUL)
-            patch_len[t] = line.size();
-        }
-        A->hstats.n_capacity_retried = todo.size();
-        g_format_counts[TF_CNT_HOST_LINES] += todo.size();
-        // (query, length) pairs: the queries as 4-byte words behind the 8-byte lengths
-        if (int rc = A->tf_patch.ensure(todo.size() * 12 + 16)) return rc;
-        for (size_t t = 0; t < todo.size(); ++t) cap[t] = (uint32_t)todo[t];
-        uint32_t *d_pq = reinterpret_cast<uint32_t *>(A->tf_patch.as<uint64_t>() + todo.size());
-        HIP_TRY(hipMemcpyAsync(A->tf_patch.p, patch_len.data(), todo.size() * 8, hipMemcpyHostToDevice, A->hstream));
-        HIP_TRY(hipMemcpyAsync(d_pq, cap.data(), todo.size() * 4, hipMemcpyHostToDevice, A->hstream));
-        HIP_TRY((hipError_t)mgx_launch_format_patch(d_len, d_pq, A->tf_patch.as<uint64_t>(), (uint32_t)todo.size(), A->hstream));
-        if (int rc = scan()) return rc;
-        HIP_TRY(d2h(counters, d_begin + n, 8));
-        HIP_TRY(hipStreamSynchronize(A->hstream));   // (patch_len and cap are read by the copies above)
-    }
-    // pass 2: the text
-    const uint64_t text_bytes = counters[0];
-    if (int rc = A->tf_text.ensure(text_bytes + 16)) return rc;
-    if (text_bytes + 1 > A->h_text_bytes) {
-        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
-        const size_t want = text_bytes + text_bytes / 8 + 4096;
-        void *p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(MGX_ERR_OOM, "hipHostMalloc(%zu) failed", want); }
-        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
-    }
-    b.text = A->tf_text.as<char>();
-    HIP_TRY((hipError_t)mgx_launch_format_write(&b, A->hstream));
-    ++g_format_counts[TF_CNT_WRITE];
-    g_format_counts[TF_CNT_D2H_BYTES] += text_bytes;
-    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
-    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
-    for (size_t t = 0; t < todo.size(); ++t) memcpy(A->h_text + A->h_line_begin[todo[t]], host_lines[t].data(), host_lines[t].size());
-    out->text = A->h_text;
-    return MGX_OK;
+    job.host_line = [&](const mgx_results &v, const char *header, const char *query, size_t qlen) {
+        return host_formatted([&](char *buf, size_t buf_len) {
+            return mgx_format_tsv_labeled(&v, 0, header, query, qlen, A->cfg.min_path_score, names.data(), n_label_names, buf, buf_len);
+        });
+    };
+    return format_on_device(A, job, out);
 }
 
-// ---- the text of `align --map` for a batch, written by kernels (map_format.hpp, mgx_mapfmt.hip) -------------
+// ---- the text of `align --map` for a batch (map_format.hpp, mgx_mapfmt.hip) ---------------------------------
 enum { MF_CNT_SIZE = 0, MF_CNT_WRITE, MF_CNT_D2H_BYTES, MF_CNT_H2D_BYTES };
 static std::atomic<uint64_t> g_mapfmt_counts[4];        // mgx_format_map_kernel_launch_counts
 void mgx_format_map_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_mapfmt_counts[x].load(); }
@@ -2352,14 +2414,6 @@ int mgx_format_map_batch(mgx_aligner *A, const char *headers, const uint64_t *he
     if (n >= 0x7FFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_map_batch: more than 2^31 - 2 queries in a batch");
     if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
     HIP_TRY(hipSetDevice(A->graph->device));
-    auto d2h = [&](void *dst, const void *src, size_t bytes) {
-        g_mapfmt_counts[MF_CNT_D2H_BYTES] += bytes;
-        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
-    };
-    auto h2d = [&](void *dst, const void *src, size_t bytes) {
-        g_mapfmt_counts[MF_CNT_H2D_BYTES] += bytes;
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, A->hstream);
-    };
     const uint32_t k = A->graph->g.k, map_length = A->ms_map_length;
     const bool sub_k = map_length != 0 && map_length < k;
     const uint32_t window = sub_k ? map_length : k;
@@ -2373,55 +2427,28 @@ int mgx_format_map_batch(mgx_aligner *A, const char *headers, const uint64_t *he
     if (presence)
         for (size_t n_kmers = 0; n_kmers <= max_kmers; ++n_kmers)
             threshold[n_kmers] = mf_threshold_host(n_kmers, discovery_fraction, sub_k);
-    const uint64_t header_bytes = header_offsets[n];
-    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
-    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
-    if (int rc = A->mf_threshold.ensure(threshold.size() * 8)) return rc;
-    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
-    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
-    if (header_bytes) HIP_TRY(h2d(A->tf_headers.p, headers, header_bytes));
-    HIP_TRY(h2d(A->tf_header_offsets.p, header_offsets, (n + 1) * 8));
-    HIP_TRY(h2d(A->mf_threshold.p, threshold.data(), threshold.size() * 8));
-    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
     MfBatch b;
-    memset(&b, 0, sizeof(b));
-    b.counts = A->ms_counts.as<uint32_t>(); b.nodes = A->ms_nodes.as<uint64_t>(); b.node_begin = A->node_begin.as<uint64_t>();
-    b.seqs = A->ms_d_seqs; b.offsets = A->ms_d_offsets;
-    b.headers = A->tf_headers.as<char>(); b.header_offsets = A->tf_header_offsets.as<uint64_t>();
-    b.threshold = A->mf_threshold.as<uint64_t>();
-    b.line_len = d_len; b.line_begin = d_begin;
-    b.n_queries = n; b.max_kmers = presence ? max_kmers : 0; b.k = k; b.window = window; b.sub_k = sub_k ? 1u : 0u; b.format = format;
-    // pass 1: the text lengths (d_len[n] = 0 closes the scan); the scan gives line_begin
-    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
-    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
-    HIP_TRY((hipError_t)mgx_launch_mapfmt_size(&b, A->hstream));
-    ++g_mapfmt_counts[MF_CNT_SIZE];
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
-    if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
-    // the counters, one copy like mgx_format_tsv_batch's: the text's bytes and a second word that is reserved (0: this formatter
-    // leaves no line to the host)
-    uint64_t counters[2] = { 0, 0 };
-    HIP_TRY(d2h(counters, d_begin + n, 16));
-    // pass 2: the text
-    const uint64_t text_bytes = counters[0];
-    if (int rc = A->tf_text.ensure(text_bytes + 16)) return rc;
-    if (text_bytes + 1 > A->h_text_bytes) {
-        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
-        const size_t want = text_bytes + text_bytes / 8 + 4096;
-        void *p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(MGX_ERR_OOM, "hipHostMalloc(%zu) failed", want); }
-        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
-    }
-    b.text = A->tf_text.as<char>();
-    HIP_TRY((hipError_t)mgx_launch_mapfmt_write(&b, A->hstream));
-    ++g_mapfmt_counts[MF_CNT_WRITE];
-    g_mapfmt_counts[MF_CNT_D2H_BYTES] += text_bytes;
-    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
-    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
-    out->text = A->h_text;
-    return MGX_OK;
+    FormatJob job = {};
+    job.fn = "mgx_format_map_batch"; job.oom_advice = "";
+    job.size_launches = &g_mapfmt_counts[MF_CNT_SIZE]; job.write_launches = &g_mapfmt_counts[MF_CNT_WRITE];
+    job.d2h_bytes = &g_mapfmt_counts[MF_CNT_D2H_BYTES]; job.h2d_bytes = &g_mapfmt_counts[MF_CNT_H2D_BYTES];
+    job.launch_size = mgx_launch_mapfmt_size; job.launch_write = mgx_launch_mapfmt_write; job.params = &b; job.text = &b.text;
+    job.headers = headers; job.header_offsets = header_offsets;
+    job.n = job.n_batch = n;
+    job.bind = [&]() -> int {
+        if (int rc = A->mf_threshold.ensure(threshold.size() * 8)) return rc;
+        g_mapfmt_counts[MF_CNT_H2D_BYTES] += threshold.size() * 8;
+        HIP_TRY(hipMemcpyAsync(A->mf_threshold.p, threshold.data(), threshold.size() * 8, hipMemcpyHostToDevice, A->hstream));
+        memset(&b, 0, sizeof(b));
+        b.counts = A->ms_counts.as<uint32_t>(); b.nodes = A->ms_nodes.as<uint64_t>(); b.node_begin = A->node_begin.as<uint64_t>();
+        b.seqs = A->ms_d_seqs; b.offsets = A->ms_d_offsets;
+        b.headers = A->tf_headers.as<char>(); b.header_offsets = A->tf_header_offsets.as<uint64_t>();
+        b.threshold = A->mf_threshold.as<uint64_t>();
+        b.line_len = A->tf_len.as<uint64_t>(); b.line_begin = A->tf_begin.as<uint64_t>();
+        b.n_queries = n; b.max_kmers = presence ? max_kmers : 0; b.k = k; b.window = window; b.sub_k = sub_k ? 1u : 0u; b.format = format;
+        return MGX_OK;
+    };
+    return format_on_device(A, job, out);            // (no host_line: this formatter leaves no line to the host)
 }
 
 // ---- metagraph align --json (cli/align.cpp:287-305): Alignment::to_json (alignment.cpp:883-963) + path_json (:704-881),
@@ -2572,7 +2599,7 @@ size_t mgx_format_json(const mgx_results *res, uint64_t qi, const char *header, 
     return s.size();
 }
 
-// ---- the `align --json` text of a range of a batch, written by kernels (json_format.hpp, mgx_jsonfmt.hip) --------
+// ---- the `align --json` text of a range of a batch (json_format.hpp, mgx_jsonfmt.hip) -------------------------
 enum { JF_CNT_SIZE = 0, JF_CNT_WRITE, JF_CNT_HOST_QUERIES, JF_CNT_D2H_BYTES };
 static std::atomic<uint64_t> g_jsonfmt_counts[4];       // mgx_format_json_kernel_launch_counts
 void mgx_format_json_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_jsonfmt_counts[x].load(); }
@@ -2595,117 +2622,29 @@ int mgx_format_json_batch(mgx_aligner *A, const char *headers, const uint64_t *h
                                      "map / summary call ran since");
     if (n >= 0x7FFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "mgx_format_json_batch: more than 2^31 - 2 queries in a range");
     HIP_TRY(hipSetDevice(A->graph->device));
-    auto d2h = [&](void *dst, const void *src, size_t bytes) {
-        g_jsonfmt_counts[JF_CNT_D2H_BYTES] += bytes;
-        return copy_sync(A, dst, src, bytes, hipMemcpyDeviceToHost);
-    };
-    // the range's headers and their offsets (as the caller counts them: the kernels subtract the first one)
-    const uint64_t header_from = header_offsets[0], header_bytes = header_offsets[n] - header_from;
-    if (int rc = A->tf_headers.ensure(header_bytes + 16)) return rc;
-    if (int rc = A->tf_header_offsets.ensure((n + 1) * 8)) return rc;
-    if (int rc = A->tf_len.ensure((n + 1) * 8)) return rc;
-    if (int rc = A->tf_begin.ensure((n + 2) * 8)) return rc;
-    if (int rc = A->tf_cap.ensure((n + 1) * 4)) return rc;
-    if (header_bytes) HIP_TRY(hipMemcpyAsync(A->tf_headers.p, headers + header_from, header_bytes, hipMemcpyHostToDevice, A->hstream));
-    HIP_TRY(hipMemcpyAsync(A->tf_header_offsets.p, header_offsets, (n + 1) * 8, hipMemcpyHostToDevice, A->hstream));
-    uint64_t *d_len = A->tf_len.as<uint64_t>(), *d_begin = A->tf_begin.as<uint64_t>();
+    const uint32_t k = A->graph->g.k;
     JfBatch b;
-    memset(&b, 0, sizeof(b));
-    b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
-    b.seqs = A->last_d_seqs; b.offsets = A->last_d_offsets;
-    b.headers = A->tf_headers.as<char>(); b.header_from = header_from; b.header_offsets = A->tf_header_offsets.as<uint64_t>();
-    b.line_len = d_len; b.line_begin = d_begin;
-    b.cap_list = A->tf_cap.as<uint32_t>(); b.cap_count = reinterpret_cast<unsigned long long *>(d_begin + n + 1);
-    b.first = first; b.n_queries = n; b.k = A->graph->g.k; b.labeled = A->anno ? 1u : 0u;
-    // pass 1: the lengths (d_len[n] = 0 closes the scan), the capacity-status queries; the scan gives line_begin
-    HIP_TRY(hipMemsetAsync(d_len + n, 0, 8, A->hstream));
-    HIP_TRY(hipMemsetAsync(d_begin + n + 1, 0, 8, A->hstream));
-    HIP_TRY((hipError_t)mgx_launch_jsonfmt_size(&b, A->hstream));
-    ++g_jsonfmt_counts[JF_CNT_SIZE];
-    auto scan = [&]() -> int {
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
-        if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_len, d_begin, (int)(n + 1), A->hstream));
+    FormatJob job = {};
+    job.fn = "mgx_format_json_batch"; job.oom_advice = ": take a smaller range";
+    job.size_launches = &g_jsonfmt_counts[JF_CNT_SIZE]; job.write_launches = &g_jsonfmt_counts[JF_CNT_WRITE];
+    job.d2h_bytes = &g_jsonfmt_counts[JF_CNT_D2H_BYTES]; job.host_lines = &g_jsonfmt_counts[JF_CNT_HOST_QUERIES];
+    job.launch_size = mgx_launch_jsonfmt_size; job.launch_write = mgx_launch_jsonfmt_write; job.params = &b; job.text = &b.text;
+    job.headers = headers; job.header_offsets = header_offsets; job.header_from = header_offsets[0];    // (the kernels subtract it)
+    job.first = first; job.n = n; job.n_batch = n_batch;
+    job.bind = [&]() -> int {
+        memset(&b, 0, sizeof(b));
+        b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
+        b.seqs = A->last_d_seqs; b.offsets = A->last_d_offsets;
+        b.headers = A->tf_headers.as<char>(); b.header_from = job.header_from; b.header_offsets = A->tf_header_offsets.as<uint64_t>();
+        b.line_len = A->tf_len.as<uint64_t>(); b.line_begin = A->tf_begin.as<uint64_t>();
+        b.cap_list = A->tf_cap.as<uint32_t>(); b.cap_count = reinterpret_cast<unsigned long long *>(A->tf_begin.as<uint64_t>() + n + 1);
+        b.first = first; b.n_queries = n; b.k = k; b.labeled = A->anno ? 1u : 0u;
         return MGX_OK;
     };
-    if (int rc = scan()) return rc;
-    uint64_t counters[2] = { 0, 0 };                  // the text's bytes, the capacity-status queries
-    HIP_TRY(d2h(counters, d_begin + n, 16));
-    // the capacity-status queries of the range: aligned again with larger limits, formatted by mgx_format_json, lengths patched in
-    std::vector<uint64_t> todo;
-    std::vector<std::string> host_lines;
-    if (counters[1]) {
-        std::vector<uint32_t> cap(counters[1]);
-        HIP_TRY(d2h(cap.data(), A->tf_cap.p, cap.size() * 4));
-        std::sort(cap.begin(), cap.end());
-        for (uint32_t i : cap) todo.push_back(first + i);
-        if (!A->retry_capacity)
-            return fail(MGX_ERR_CAPACITY, "mgx_format_json_batch: query %llu (and %llu more) has a capacity status and retry_capacity is off",
-                        (unsigned long long)todo.front(), (unsigned long long)todo.size() - 1);
-        std::vector<HostResults> fixed;
-        std::vector<uint8_t> have;
-        std::vector<uint64_t> h_off;
-        std::vector<char> h_seq;
-        if (int rc = realign_capacity_queries(A, A->last_d_seqs, A->last_d_offsets, n_batch, todo, fixed, have, h_off, h_seq)) return rc;
-        g_jsonfmt_counts[JF_CNT_D2H_BYTES] += (n_batch + 1) * 8 + (h_seq.size() - 1);
-        std::vector<uint64_t> patch_len(todo.size());
-        host_lines.resize(todo.size());
-        for (size_t t = 0; t < todo.size(); ++t) {
-            const uint64_t q = todo[t];
-            if (!have[t])
-                return fail(MGX_ERR_CAPACITY, "mgx_format_json_batch: query %llu keeps its capacity status after the retry", (unsigned long long)q);
-            mgx_results v;
-            fixed[t].view(&v);
-            const std::string header(headers + header_offsets[q - first], headers + header_offsets[q - first + 1]);
-            const char *query = h_seq.data() + (h_off[q] - h_off[todo.front()]);
-            const size_t qlen = h_off[q + 1] - h_off[q];
-            std::string &line = host_lines[t];
-            line.resize(mgx_format_json(&v, 0, header.c_str(), query, qlen, b.k, nullptr, 0) + 1);
-            mgx_format_json(&v, 0, header.c_str(), query, qlen, b.k, &line[0], line.size());
-            line.pop_back();                         // (the formatter's NUL)
-            patch_len[t] = line.size();
-        }
-        A->hstats.n_capacity_retried = todo.size();
-        g_jsonfmt_counts[JF_CNT_HOST_QUERIES] += todo.size();
-        // (i, length) pairs: the i as 4-byte words behind the 8-byte lengths
-        if (int rc = A->tf_patch.ensure(todo.size() * 12 + 16)) return rc;
-        uint32_t *d_pq = reinterpret_cast<uint32_t *>(A->tf_patch.as<uint64_t>() + todo.size());
-        HIP_TRY(hipMemcpyAsync(A->tf_patch.p, patch_len.data(), todo.size() * 8, hipMemcpyHostToDevice, A->hstream));
-        HIP_TRY(hipMemcpyAsync(d_pq, cap.data(), todo.size() * 4, hipMemcpyHostToDevice, A->hstream));
-        HIP_TRY((hipError_t)mgx_launch_format_patch(d_len, d_pq, A->tf_patch.as<uint64_t>(), (uint32_t)todo.size(), A->hstream));
-        if (int rc = scan()) return rc;
-        HIP_TRY(d2h(counters, d_begin + n, 8));
-        HIP_TRY(hipStreamSynchronize(A->hstream));   // (patch_len and cap are read by the copies above)
-    }
-    // pass 2: the text
-    const uint64_t text_bytes = counters[0];
-    if (A->tf_text.ensure(text_bytes + 16) != MGX_OK)
-        return fail(MGX_ERR_OOM, "mgx_format_json_batch: the text of queries %llu .. %llu needs %llu bytes and no device buffer of that size "
-                                 "could be allocated: take a smaller range", (unsigned long long)first, (unsigned long long)(first + n),
-                    (unsigned long long)text_bytes);
-    if (text_bytes + 1 > A->h_text_bytes) {
-        if (A->h_text) { (void)hipHostFree(A->h_text); A->h_text = nullptr; A->h_text_bytes = 0; }
-        const size_t want = text_bytes + text_bytes / 8 + 4096;
-        void *p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            out->text = "";
-            return fail(MGX_ERR_OOM, "mgx_format_json_batch: the text of queries %llu .. %llu needs %llu bytes and no pinned host buffer of "
-                                     "that size could be allocated: take a smaller range", (unsigned long long)first,
-                        (unsigned long long)(first + n), (unsigned long long)text_bytes);
-        }
-        A->h_text = static_cast<char *>(p); A->h_text_bytes = want;
-    }
-    b.text = A->tf_text.as<char>();
-    HIP_TRY((hipError_t)mgx_launch_jsonfmt_write(&b, A->hstream));
-    ++g_jsonfmt_counts[JF_CNT_WRITE];
-    g_jsonfmt_counts[JF_CNT_D2H_BYTES] += text_bytes;
-    if (text_bytes) HIP_TRY(hipMemcpyAsync(A->h_text, A->tf_text.p, text_bytes, hipMemcpyDeviceToHost, A->hstream));
-    HIP_TRY(d2h(A->h_line_begin.data(), d_begin, (n + 1) * 8));
-    for (size_t t = 0; t < todo.size(); ++t) memcpy(A->h_text + A->h_line_begin[todo[t] - first], host_lines[t].data(), host_lines[t].size());
-    out->text = A->h_text;
-    return MGX_OK;
+    job.host_line = [&](const mgx_results &v, const char *header, const char *query, size_t qlen) {
+        return host_formatted([&](char *buf, size_t buf_len) { return mgx_format_json(&v, 0, header, query, qlen, k, buf, buf_len); });
+    };
+    return format_on_device(A, job, out);
 }
 
 } // extern "C"

@@ -155,6 +155,23 @@ class HipGraphSet {
     std::vector<std::unique_ptr<HipBOSSGraph>> replicas_;
 };
 
+// what the format_batch* methods of the two handle classes below share (no part of the interface)
+namespace detail {
+constexpr uint64_t ANY_BATCH = ~0ull;
+// the view of the text a mgx_format_*_batch call (`fn`) returned with `rc`; n_queries: the size the handle's batch must have
+inline std::string_view text_view(int rc, const mgx_text &text, const char *fn, uint64_t n_queries = ANY_BATCH) {
+    if (rc) throw std::runtime_error(std::string(fn) + ": " + mgx_last_error() + " (" + std::to_string(rc) + ")");
+    if (n_queries != ANY_BATCH && text.n_queries != n_queries) throw std::runtime_error(std::string(fn) + ": the handle's batch is not this one");
+    return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+}
+// name_offsets[0 .. n] counted from name_offsets[0]
+inline std::vector<uint64_t> rebased(const uint64_t *name_offsets, uint64_t n) {
+    std::vector<uint64_t> offsets(n + 1);
+    for (uint64_t t = 0; t <= n; ++t) offsets[t] = name_offsets[t] - name_offsets[0];
+    return offsets;
+}
+}  // namespace detail
+
 // DeBruijnGraph::map_to_nodes / DeBruijnGraph::find on the device graph — the graph-side calls behind `metagraph align --map`
 // (map_sequences_in_file, cli/align.cpp:71-179).  Holds a device handle of its own; one per worker thread.  The batched form is
 // the one to use: a single sequence pays a whole launch.
@@ -193,13 +210,10 @@ class HipGraphMapper {
     // mgx_format_map gives for every query, in query order.  names / name_offsets: the headers as flat arrays, `name_offsets`
     // points at the batch's first record (n + 1 entries).  The view is the handle's and stays valid until its next batch.
     std::string_view format_batch(const char *names, const uint64_t *name_offsets, uint64_t n, int format, double discovery_fraction) const {
-        std::vector<uint64_t> offsets(n + 1);
-        for (uint64_t t = 0; t <= n; ++t) offsets[t] = name_offsets[t] - name_offsets[0];
+        const std::vector<uint64_t> offsets = detail::rebased(name_offsets, n);
         mgx_text text{};
-        if (int rc = mgx_format_map_batch(a_, names + name_offsets[0], offsets.data(), format, discovery_fraction, &text))
-            throw std::runtime_error(std::string("mgx_format_map_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
-        if (text.n_queries != n) throw std::runtime_error("mgx_format_map_batch: the handle's batch is not this one");
-        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+        const int rc = mgx_format_map_batch(a_, names + name_offsets[0], offsets.data(), format, discovery_fraction, &text);
+        return detail::text_view(rc, text, "mgx_format_map_batch", n);
     }
     // std::vector<node_index> map_to_nodes(const DeBruijnGraph &, std::string_view) (sequence_graph.cpp)
     std::vector<uint64_t> map_to_nodes(std::string_view sequence) const {
@@ -358,18 +372,8 @@ class HipDBGAligner : public IDBGAligner {
     // on the host only: align_batch with a callback remains the path) and for capacity statuses no retry cures.
     std::string_view format_batch_tsv(const std::vector<Query> &seq_batch, const std::vector<std::string> *label_names = nullptr) const {
         std::string headers;
-        std::vector<uint64_t> offsets(seq_batch.size() + 1, 0);
-        for (size_t t = 0; t < seq_batch.size(); ++t) {
-            headers += seq_batch[t].first;
-            offsets[t + 1] = headers.size();
-        }
-        std::vector<const char *> names;
-        if (label_names) for (const std::string &nm : *label_names) names.push_back(nm.c_str());
-        mgx_text text{};
-        if (int rc = mgx_format_tsv_batch(a_, headers.data(), offsets.data(), names.empty() ? nullptr : names.data(), (uint32_t)names.size(), &text))
-            throw std::runtime_error(std::string("mgx_format_tsv_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
-        if (text.n_queries != seq_batch.size()) throw std::runtime_error("mgx_format_tsv_batch: the handle's batch is not this one");
-        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+        const std::vector<uint64_t> offsets = pack_headers(seq_batch, 0, seq_batch.size(), headers);
+        return format_tsv(headers.data(), offsets.data(), seq_batch.size(), label_names);
     }
     // ... over reads that are in device memory already (HipReadParser::slice): n reads, offsets from 0
     void align_batch_device(const char *d_seqs, const uint64_t *d_offsets, uint64_t n) const {
@@ -378,15 +382,7 @@ class HipDBGAligner : public IDBGAligner {
     }
     // ... with the names as flat arrays (mgx_reads::names / name_offsets; `name_offsets` points at the batch's first record: n + 1 entries)
     std::string_view format_batch_tsv(const char *names, const uint64_t *name_offsets, uint64_t n, const std::vector<std::string> *label_names = nullptr) const {
-        std::vector<uint64_t> offsets(n + 1);
-        for (uint64_t t = 0; t <= n; ++t) offsets[t] = name_offsets[t] - name_offsets[0];
-        std::vector<const char *> lnames;
-        if (label_names) for (const std::string &nm : *label_names) lnames.push_back(nm.c_str());
-        mgx_text text{};
-        if (int rc = mgx_format_tsv_batch(a_, names + name_offsets[0], offsets.data(), lnames.empty() ? nullptr : lnames.data(), (uint32_t)lnames.size(), &text))
-            throw std::runtime_error(std::string("mgx_format_tsv_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
-        if (text.n_queries != n) throw std::runtime_error("mgx_format_tsv_batch: the handle's batch is not this one");
-        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+        return format_tsv(names + name_offsets[0], detail::rebased(name_offsets, n).data(), n, label_names);
     }
     // The `align --json` lines of queries first .. first + n of the batch align_batch_device ran last, written on the device
     // (mgx_format_json_batch): what mgx_format_json gives for those queries, in query order.  JSON text is large (about 60 bytes
@@ -396,12 +392,7 @@ class HipDBGAligner : public IDBGAligner {
     std::string_view format_batch_json(const std::vector<Query> &seq_batch, uint64_t first, uint64_t n) const {
         if (first > seq_batch.size() || n > seq_batch.size() - first) throw std::runtime_error("format_batch_json: the range is beyond the batch");
         std::string headers;
-        std::vector<uint64_t> offsets(n + 1, 0);
-        for (uint64_t t = 0; t < n; ++t) {
-            headers += seq_batch[first + t].first;
-            offsets[t + 1] = headers.size();
-        }
-        if (headers.empty()) headers.push_back('\0');               // (a range of empty headers still needs a pointer)
+        const std::vector<uint64_t> offsets = pack_headers(seq_batch, first, n, headers);
         return format_json_range(headers.data(), offsets.data(), first, n);
     }
     // ... with the names as flat arrays (mgx_reads::names / name_offsets; `name_offsets` points at the BATCH's first record)
@@ -444,9 +435,25 @@ class HipDBGAligner : public IDBGAligner {
     // of the caller's is ordered against it)
     std::string_view format_json_range(const char *headers, const uint64_t *header_offsets, uint64_t first, uint64_t n) const {
         mgx_text text{};
-        if (int rc = mgx_format_json_batch(a_, headers, header_offsets, first, n, &text))
-            throw std::runtime_error(std::string("mgx_format_json_batch: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
-        return std::string_view(text.text, (size_t)text.line_begin[text.n_queries]);
+        const int rc = mgx_format_json_batch(a_, headers, header_offsets, first, n, &text);
+        return detail::text_view(rc, text, "mgx_format_json_batch");
+    }
+    std::string_view format_tsv(const char *headers, const uint64_t *header_offsets, uint64_t n, const std::vector<std::string> *label_names) const {
+        std::vector<const char *> names;
+        if (label_names) for (const std::string &nm : *label_names) names.push_back(nm.c_str());
+        mgx_text text{};
+        const int rc = mgx_format_tsv_batch(a_, headers, header_offsets, names.empty() ? nullptr : names.data(), (uint32_t)names.size(), &text);
+        return detail::text_view(rc, text, "mgx_format_tsv_batch", n);
+    }
+    // the headers of seq_batch[first .. first + n) end to end in `blob` -> their n + 1 offsets
+    static std::vector<uint64_t> pack_headers(const std::vector<Query> &seq_batch, uint64_t first, uint64_t n, std::string &blob) {
+        std::vector<uint64_t> offsets(n + 1, 0);
+        for (uint64_t t = 0; t < n; ++t) {
+            blob += seq_batch[first + t].first;
+            offsets[t + 1] = blob.size();
+        }
+        if (blob.empty()) blob.push_back('\0');                     // (a range of empty headers still needs a pointer)
+        return offsets;
     }
     void own_stream() {
         if (getenv("MGX_ADAPTER_DEFAULT_STREAM")) return;          // (A/B switch: every handle on the legacy default stream, as before round 6)

@@ -264,6 +264,52 @@ def test_capacity_statuses_are_retried_and_spliced():
     assert e.value.code == capi.MGX_ERR_CAPACITY and "query" in str(e.value)
 
 
+# ---- 8b. TSV, JSON and map texts in turn: one host pipeline, one set of buffers per handle ----------------------------------
+def test_three_forms_in_turn_on_shared_buffers():
+    """the three batch formatters run the same host sequence on the handle's tf_* buffers, scan space, pinned text and line_begin:
+    TSV, JSON, a JSON range and TSV again on one handle (some queries take the capacity retry), `align --map` texts on a second
+    handle of the same graph before and after another TSV call on the first.  Every text and line_begin equals the per-query host
+    formatters' on a default-limits aligner.  (On the CPU, emu_drv.EmuRun in its 8-lane build, the group width these batches
+    run with, aligns all reads of seed 9802 with status 0 under default limits, and leaves reads 6 and 22 a capacity status
+    with a 1600-byte cell arena: one inside the range 5 .. 12, one outside.)"""
+    from test_gpu_format_batch import host_lines as tsv_host_lines
+    from test_gpu_map_format_batch import COUNT, NODES, check_device_texts, host_texts
+    k = 21
+    g, reads = make_world(9802, k, genome_len=3000, n_reads=24, read_len=120)
+    cfg = capi.config_cli(k)
+    G = gpu_graph(g)
+    headers = ["turn%d" % i for i in range(len(reads))]
+    D = aligner.Aligner(G, cfg)                                                # the yardstick: an aligner with default limits
+    align_host(D, reads)
+    res = D.fetch()
+    assert all(res.status[i] == 0 for i in range(len(reads)))
+    want_tsv = tsv_host_lines(D, res, headers, reads)
+    want_json = host_lines(res, headers, reads, k)
+
+    def same(got, want):
+        text, lb = got
+        assert text == b"".join(want)
+        assert [int(x) for x in lb] == [0] + [int(x) for x in np.cumsum([len(w) for w in want])]
+        return text
+
+    lim = capi.Limits()
+    lim.cell_arena_bytes = 1600
+    A = aligner.Aligner(G, cfg, lim)
+    align_host(A, reads)
+    tsv = same(A.format_tsv_batch(headers), want_tsv)
+    assert A.stats()["n_capacity_retried"] > 0
+    same(A.format_json_batch(headers), want_json)
+    assert A.stats()["n_capacity_retried"] > 0
+    same(A.format_json_batch(headers[5:12], first=5, n=7), want_json[5:12])
+    assert same(A.format_tsv_batch(headers), want_tsv) == tsv
+    M = aligner.Aligner(G, cfg)                                                # a second handle: the same pool of device blocks
+    want_map = host_texts(M, headers, reads, 0, [(NODES, 0.7), (COUNT, 0.7)])
+    for _ in range(2):
+        M.map_summary(reads, keep_nodes=True)
+        check_device_texts(M, headers, want_map)
+        assert same(A.format_tsv_batch(headers), want_tsv) == tsv
+
+
 # ---- 9. refusals ----------------------------------------------------------------------------------------------------------
 def test_refusals():
     g, reads = make_world(9300, 21, genome_len=3000, n_reads=20, read_len=120)
