@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
+#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
+                                * (the mgx_results layout of a batch, written by kernels); before that mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
                                 * batch, written by kernels); before that mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
                                 * `align --map`, written by kernels); before that mgx_read_parser_* / mgx_parse_reads / mgx_parse_kernel_launch_counts (FASTA / FASTQ text to
                                 * read batches on the device); before that mgx_format_tsv_batch / mgx_format_kernel_launch_counts (the TSV text of a batch, written
@@ -291,6 +292,27 @@ int mgx_fetch_results(mgx_aligner *a, mgx_results *out);
  * 32-bit words holding nodes / packed CIGAR runs (len << 3 | op) / path characters. */
 int mgx_device_results(mgx_aligner *a, const void **headers, uint64_t *header_bytes, uint64_t *n_queries,
                        const void **stream, uint64_t *stream_words);
+/* The results of the last batch in the layout of mgx_results, decoded by kernels and LEFT IN DEVICE MEMORY — what a consumer on
+ * the device can read (mgx_device_results exposes the kernels' private record and stream encoding).  Every pointer of `out`
+ * is device memory owned by the aligner, valid until its next batch, fetch, decode or format call; `sizes` holds the element
+ * counts of alignments, nodes, cigar, seqs and labels (aln_begin has n_queries + 1 elements, status n_queries); out->labels is
+ * NULL when sizes->n_labels is 0.  Only the five totals (40 bytes) travel to the host.
+ *   - Array by array and byte for byte, padding included, `out` holds what mgx_results_from_raw_labeled gives for the records
+ *     and the stream of mgx_device_results.  That is, the results are PRE-RETRY: a query whose per-read arenas overflowed has
+ *     status MGX_ERR_CAPACITY and no alignments (mgx_fetch_results re-aligns those; this call does not).
+ *   - With post_chain_alignments the arrays hold the UNCHAINED alignments (chaining runs on the host inside mgx_fetch_results).
+ *   - Call it after mgx_align_batch_device or mgx_align_batch, while that batch is still the staged one: without an aligned
+ *     batch on the handle, or after another batch call (mgx_map_batch, mgx_map_summary_batch) staged again, MGX_ERR_INVALID.
+ *     With seqs_on_device != 0 the reads are not needed.  A batch of 0 queries: MGX_OK, all sizes 0.
+ *   - 2^31 - 1 queries or more: MGX_ERR_UNSUPPORTED.  An output buffer that cannot be allocated: MGX_ERR_OOM, naming the bytes.
+ * The same two kernels serve mgx_fetch_results / mgx_align_batch under the pipeline option decode_on_device=1
+ * (mgx_aligner_set_pipeline): the seven arrays then come to pinned host memory of the handle instead of records and stream to
+ * pageable vectors and a one-thread decode; the view returned is equal to the option-off view in every configuration. */
+typedef struct mgx_results_sizes { uint64_t n_alignments, n_nodes, n_cigar, n_seq_bytes, n_labels; } mgx_results_sizes;
+int mgx_decode_results_device(mgx_aligner *a, mgx_results *out, mgx_results_sizes *sizes);
+/* Test hook: out4 = launches of k_decode_size, launches of k_decode_write, bytes copied device-to-host by the decode,
+ * mgx_fetch_results calls the option decode_on_device served — since the library was loaded. */
+void mgx_decode_kernel_launch_counts(uint64_t *out4);
 /* Capacity (32-bit words) of the device stream buffer behind mgx_device_results: a function of the batch shape only,
  * so equal on all ranks that run equally shaped batches — the padded RCCL gather relies on it. */
 uint64_t mgx_device_stream_capacity(const mgx_aligner *a);
@@ -384,6 +406,9 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   seed_wps=4|8         wavefronts per SIMD of the short-read seeding kernel (default 8)
  *   map_pipe=0|1|2       the mapping kernel as a request / response machine: never / from 65536 chains on (default) / always
  *   retry_capacity=0     capacity statuses are handed to the caller instead of re-aligning those queries with larger limits
+ *   decode_on_device=0|1 mgx_fetch_results / mgx_align_batch decode the batch into the mgx_results layout by kernels and copy the
+ *                        seven arrays to pinned host memory (default 0: records and stream are copied, one host thread decodes);
+ *                        the view is the same.  Ignored (host decode) once the aligned batch is no longer the staged one
  *   no_compact / no_alias / no_bt_runs / no_flat = 1   A/B forms of the column records and loops
  * Unknown name: MGX_ERR_INVALID.  (Measurement probes that change results or occupancy exist only in -DMGX_PROBES builds.) */
 int mgx_aligner_set_pipeline(mgx_aligner *a, const char *name);

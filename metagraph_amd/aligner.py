@@ -223,6 +223,15 @@ class Aligner:
         _check(capi.lib().mgx_fetch_results(self.h, C.byref(res)))
         return res
 
+    def decode_device(self):
+        """mgx_decode_results_device: the results of the batch align_device / align_batch ran last in the mgx_results layout,
+        decoded by kernels and left in device memory.  -> (capi.Results whose pointers are DEVICE memory owned by the aligner —
+        not to be dereferenced on the host —, dict of the arrays' element counts: n_alignments, n_nodes, n_cigar, n_seq_bytes,
+        n_labels).  Pre-retry: a capacity-status query has its status and no alignments."""
+        res, sizes = capi.Results(), capi.ResultsSizes()
+        _check(capi.lib().mgx_decode_results_device(self.h, C.byref(res), C.byref(sizes)))
+        return res, {f[0]: int(getattr(sizes, f[0])) for f in capi.ResultsSizes._fields_}
+
     def map_batch(self, queries):
         blob, offs = pack_queries(queries)
         m = capi.Mapping()
@@ -441,6 +450,12 @@ def format_json_kernel_launch_counts():
     """mgx_format_json_kernel_launch_counts -> (size kernel launches, write kernel launches, queries formatted on the host, bytes
     copied device-to-host by format_json_batch) since the library was loaded"""
     return _four_counts(capi.lib().mgx_format_json_kernel_launch_counts)
+
+
+def decode_kernel_launch_counts():
+    """mgx_decode_kernel_launch_counts -> (size kernel launches, write kernel launches, bytes copied device-to-host by the decode,
+    mgx_fetch_results calls the option decode_on_device served) since the library was loaded"""
+    return _four_counts(capi.lib().mgx_decode_kernel_launch_counts)
 
 
 def format_map_kernel_launch_counts():

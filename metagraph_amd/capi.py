@@ -66,6 +66,12 @@ class Results(C.Structure):
                 ("labels", C.POINTER(C.c_uint32))]
 
 
+class ResultsSizes(C.Structure):
+    """mgx_results_sizes: the element counts of the arrays of a Results view in device memory (mgx_decode_results_device)"""
+    _fields_ = [("n_alignments", C.c_uint64), ("n_nodes", C.c_uint64), ("n_cigar", C.c_uint64), ("n_seq_bytes", C.c_uint64),
+                ("n_labels", C.c_uint64)]
+
+
 class Mapping(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("node_begin", C.POINTER(C.c_uint64)),
                 ("nodes_fwd", C.POINTER(C.c_uint64)), ("nodes_rc", C.POINTER(C.c_uint64))]
@@ -303,6 +309,9 @@ def lib():
     L.mgx_format_json_batch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(Text)]
     L.mgx_format_json_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.mgx_format_json_kernel_launch_counts.restype = None
+    L.mgx_decode_results_device.argtypes = [C.c_void_p, C.POINTER(Results), C.POINTER(ResultsSizes)]
+    L.mgx_decode_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_decode_kernel_launch_counts.restype = None
     L.mgx_read_parser_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_read_parser_destroy.argtypes = [C.c_void_p]
     L.mgx_read_parser_destroy.restype = None

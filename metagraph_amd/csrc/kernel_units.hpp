@@ -17,6 +17,7 @@ constexpr size_t MGX_FORMAT_ARGS_BYTES = 128;           // sizeof(TfBatch), tsv_
 constexpr size_t MGX_PARSE_ARGS_BYTES = 144;            // sizeof(RpChunk), reads_parse.hpp
 constexpr size_t MGX_MAPFMT_ARGS_BYTES = 120;           // sizeof(MfBatch), map_format.hpp
 constexpr size_t MGX_JSONFMT_ARGS_BYTES = 120;          // sizeof(JfBatch), json_format.hpp
+constexpr size_t MGX_DECODE_ARGS_BYTES = 104;           // sizeof(RdBatch), results_decode.hpp
 
 struct mgx_annotation;
 
@@ -90,6 +91,12 @@ int mgx_launch_mapfmt_write(const void *args, void *stream);
 // text + line_begin[i].  (The lengths of host-formatted lines are patched in by mgx_launch_format_patch.)
 int mgx_launch_jsonfmt_size(const void *args, void *stream);
 int mgx_launch_jsonfmt_write(const void *args, void *stream);
+
+// mgx_decode.hip: the results of a batch in the layout of mgx_results (results_decode.hpp).  args: an RdBatch (host memory).  size:
+// counts[x * stride + q] for the five arrays x and every query q, and zeros at q = n_queries; write: status[q] and the alignments,
+// nodes, CIGAR runs, path characters and labels of every query at begins[x * stride + q].
+int mgx_launch_decode_size(const void *args, void *stream);
+int mgx_launch_decode_write(const void *args, void *stream);
 
 // mgx_parse.hip: FASTA / FASTQ text to read batches (reads_parse.hpp).  args: an RpChunk (host memory).  count: the '\n' mask and
 // count of every 64-byte span; table: line_begin[] from the masks and the scanned counts; classify: what every line adds (items);

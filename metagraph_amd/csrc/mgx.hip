@@ -30,10 +30,27 @@
 #include "tsv_format.hpp"
 #include "map_format.hpp"
 #include "json_format.hpp"
+#include "results_decode.hpp"
 
 using namespace mgx;
 static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES && sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES
               && sizeof(SeedLaneParams) == MGX_SEED_LANE_PARAMS_BYTES, "a parameter block differs from what the kernel units take");
+// the records the decode kernels write (results_decode.hpp) are the public ones, field by field
+static_assert(sizeof(RdBatch) == MGX_DECODE_ARGS_BYTES, "RdBatch differs from what mgx_decode.hip takes");
+static_assert(sizeof(RdCigarOp) == sizeof(mgx_cigar_op) && offsetof(RdCigarOp, len) == offsetof(mgx_cigar_op, len)
+              && offsetof(RdCigarOp, op) == offsetof(mgx_cigar_op, op) && offsetof(RdCigarOp, pad) == offsetof(mgx_cigar_op, _pad),
+              "RdCigarOp is not mgx_cigar_op");
+static_assert(sizeof(RdAlignment) == sizeof(mgx_alignment) && offsetof(RdAlignment, score) == offsetof(mgx_alignment, score)
+              && offsetof(RdAlignment, offset) == offsetof(mgx_alignment, offset) && offsetof(RdAlignment, clipping) == offsetof(mgx_alignment, clipping)
+              && offsetof(RdAlignment, end_clipping) == offsetof(mgx_alignment, end_clipping)
+              && offsetof(RdAlignment, num_matches) == offsetof(mgx_alignment, num_matches) && offsetof(RdAlignment, n_nodes) == offsetof(mgx_alignment, n_nodes)
+              && offsetof(RdAlignment, n_cigar) == offsetof(mgx_alignment, n_cigar) && offsetof(RdAlignment, seq_len) == offsetof(mgx_alignment, seq_len)
+              && offsetof(RdAlignment, nodes_begin) == offsetof(mgx_alignment, nodes_begin)
+              && offsetof(RdAlignment, cigar_begin) == offsetof(mgx_alignment, cigar_begin) && offsetof(RdAlignment, seq_begin) == offsetof(mgx_alignment, seq_begin)
+              && offsetof(RdAlignment, orientation) == offsetof(mgx_alignment, orientation) && offsetof(RdAlignment, pad) == offsetof(mgx_alignment, _pad)
+              && offsetof(RdAlignment, n_labels) == offsetof(mgx_alignment, n_labels) && offsetof(RdAlignment, labels_begin) == offsetof(mgx_alignment, labels_begin),
+              "RdAlignment is not mgx_alignment");
+static_assert(sizeof(mgx_results_sizes) == RD_ARRAYS * 8, "mgx_results_sizes is the five totals in the order of RdArray");
 
 // =================================================================================================
 // kernels
@@ -619,6 +636,13 @@ struct mgx_aligner {
     char *h_text = nullptr;                      // the text on the host: pinned memory, grown as needed
     size_t h_text_bytes = 0;
     std::vector<uint64_t> h_line_begin;
+    // decode_on_device (mgx_decode_results_device, the option decode_on_device): the five count arrays and their exclusive sums
+    // (RD_ARRAYS x (n + 1) words each; the first of the sums is aln_begin), the five totals, and the other six output arrays
+    DevBuf rd_counts, rd_begins, rd_totals, rd_alns, rd_nodes, rd_cigar, rd_seqs, rd_status, rd_labels;
+    enum { RD_H_ALN_BEGIN = 0, RD_H_ALNS, RD_H_NODES, RD_H_CIGAR, RD_H_SEQS, RD_H_STATUS, RD_H_LABELS, RD_H_N };
+    void *h_rd[RD_H_N] = {};                     // the seven arrays on the host: pinned memory, grown as needed (like h_text)
+    size_t h_rd_bytes[RD_H_N] = {};
+    bool aligned_empty = false;                  // the last mgx_align_batch_device call had no query (it stages nothing)
     mgx_stats hstats;
     hipEvent_t ev[EV_COUNT] = {};
     uint64_t kernels_ran = 0;     // MGX_KERNEL_* bits of the extension kernels the last batch launched
@@ -640,6 +664,7 @@ struct mgx_aligner {
         int seed_wps = 8;         // wavefronts per SIMD of the short-read seeding kernel: 8 (64 VGPRs, spills) or 4 (102 VGPRs, tables in LDS)
         int device_share = 1;     // handles expected to run on this device at the same time (worker threads, -p N): the per-slot
                                   // arenas of this handle are sized for 1 / device_share of the machine instead of all of it
+        int decode_on_device = 0; // mgx_fetch_results: the mgx_results arrays written by kernels (decode_on_device below) instead of HostResults::decode
         int map_pipe = 1;         // k_map as the request / response machine (map_pipe.hpp): 1 = for batches of >= 65536 chains, 2 = always,
                                   // 0 = never (one chain step per lane and iteration: rounds 1-4)
     } opt;
@@ -928,7 +953,8 @@ static int aligner_create(const mgx_graph *g, const mgx_config *config, const mg
                        &A->work_key_sorted, &A->order_in, &A->order, &A->sort_tmp, &A->retry_list, &A->resume_pool[0], &A->resume_pool[1],
                        &A->retry_list2, &A->retry_key[0], &A->retry_key[1], &A->lane_scratch, &A->lane_params, &A->lane_bail, &A->lane_hist, &A->seedlane_scratch, &A->seedlane_params,
                        &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted, &A->mf_threshold, &A->tf_headers, &A->tf_header_offsets,
-                       &A->tf_names, &A->tf_len, &A->tf_begin, &A->tf_text, &A->tf_cap, &A->tf_patch })
+                       &A->tf_names, &A->tf_len, &A->tf_begin, &A->tf_text, &A->tf_cap, &A->tf_patch, &A->rd_counts, &A->rd_begins, &A->rd_totals, &A->rd_alns,
+                       &A->rd_nodes, &A->rd_cigar, &A->rd_seqs, &A->rd_status, &A->rd_labels })
         b->pooled = true;
     {
         std::string err;
@@ -1009,6 +1035,7 @@ void mgx_aligner_destroy(mgx_aligner *a) {
     (void)hipStreamSynchronize(a->hstream);
     for (auto &e : a->ev) if (e) (void)hipEventDestroy(e);
     if (a->h_text) (void)hipHostFree(a->h_text);
+    for (void *p : a->h_rd) if (p) (void)hipHostFree(p);
     if (a->own_stream) (void)hipStreamDestroy(a->hstream);
     delete a;
 }
@@ -1845,6 +1872,7 @@ int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
         else if (key == "groups_per_wave") o.groups_per_wave = std::min(8, v);
         else if (key == "multi_pass") o.multi_pass = v;
         else if (key == "no_compact") o.no_compact = v;
+        else if (key == "decode_on_device") o.decode_on_device = v != 0;
         else if (key == "no_alias") o.no_alias = v;
         else if (key == "no_bt_runs") o.no_bt_runs = v;
         else if (key == "no_flat") o.no_flat = v;
@@ -1883,7 +1911,8 @@ int mgx_align_batch_device(mgx_aligner *A, const char *seqs, const uint64_t *off
     if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
     HIP_TRY(hipSetDevice(A->graph->device));
     const char *d_seqs; const uint64_t *d_offsets; uint32_t Lmax;
-    if (n == 0) { A->n_reads = 0; return MGX_OK; }
+    if (n == 0) { A->n_reads = 0; A->aligned_empty = true; return MGX_OK; }
+    A->aligned_empty = false;
     { HostStageTimer t("stage_batch"); if (int rc = stage_batch(A, seqs, offsets, n, on_device, &d_seqs, &d_offsets, &Lmax)) return rc; }
     A->last_d_seqs = d_seqs; A->last_d_offsets = d_offsets; A->aligned_generation = A->stage_generation;
     bool mapped = A->cfg.max_seed_length >= A->graph->g.k;
@@ -1910,24 +1939,158 @@ int mgx_align_batch_device(mgx_aligner *A, const char *seqs, const uint64_t *off
 
 static int retry_capacity_queries(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, mgx_results *out);
 
+// ---- the mgx_results layout of a batch, written by kernels (results_decode.hpp, mgx_decode.hip): the one host
+// sequence behind mgx_decode_results_device (RD_TO_DEVICE: `out` points at the device arrays) and the option decode_on_device of
+// mgx_fetch_results (RD_TO_HOST: the seven arrays are copied to the handle's pinned buffers).  The caller has checked that the
+// aligned batch is the staged one and that n = A->n_reads > 0.
+enum { RD_CNT_SIZE = 0, RD_CNT_WRITE, RD_CNT_D2H_BYTES, RD_CNT_FETCHES };
+static std::atomic<uint64_t> g_decode_counts[4];        // mgx_decode_kernel_launch_counts
+void mgx_decode_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 4; ++x) out4[x] = g_decode_counts[x].load(); }
+
+enum RdWhere { RD_TO_DEVICE, RD_TO_HOST };
+static int decode_on_device(mgx_aligner *A, RdWhere where, mgx_results *out, mgx_results_sizes *sizes) {
+    const char *fn = where == RD_TO_DEVICE ? "mgx_decode_results_device" : "mgx_fetch_results (decode_on_device=1)";
+    const uint64_t n = A->n_reads;
+    if (n >= 0x7FFFFFFFull) return fail(MGX_ERR_UNSUPPORTED, "%s: more than 2^31 - 2 queries in a batch", fn);
+    const uint64_t stride = n + 1;
+    if (int rc = A->rd_counts.ensure(RD_ARRAYS * stride * 8)) return rc;
+    if (int rc = A->rd_begins.ensure(RD_ARRAYS * stride * 8)) return rc;
+    if (int rc = A->rd_totals.ensure(RD_ARRAYS * 8)) return rc;
+    if (int rc = A->rd_status.ensure(n * 4 + 16)) return rc;
+    uint64_t *d_counts = A->rd_counts.as<uint64_t>(), *d_begins = A->rd_begins.as<uint64_t>();
+    RdBatch b;
+    memset(&b, 0, sizeof(b));
+    b.results = A->results.as<ReadResult>(); b.stream = A->stream.as<uint32_t>();
+    b.counts = d_counts; b.begins = d_begins; b.status = A->rd_status.as<int32_t>();
+    b.n_queries = n; b.stride = stride; b.labeled = A->anno ? 1u : 0u;
+    // pass 1: what every query takes in the five arrays (and the zeros that close the scans); the scans give the begins
+    HIP_TRY((hipError_t)mgx_launch_decode_size(&b, A->hstream));
+    ++g_decode_counts[RD_CNT_SIZE];
+    for (int x = 0; x < RD_ARRAYS; ++x) {
+        size_t tmp_bytes = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_counts + x * stride, d_begins + x * stride, (int)(n + 1), A->hstream));
+        if (int rc = A->scan_tmp.ensure(tmp_bytes + 16)) return rc;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A->scan_tmp.p, tmp_bytes, d_counts + x * stride, d_begins + x * stride, (int)(n + 1), A->hstream));
+        // the totals side by side, so that one copy of 40 bytes brings them
+        HIP_TRY(hipMemcpyAsync(A->rd_totals.as<uint64_t>() + x, d_begins + x * stride + n, 8, hipMemcpyDeviceToDevice, A->hstream));
+    }
+    uint64_t total[RD_ARRAYS] = { 0, 0, 0, 0, 0 };
+    HIP_TRY(copy_sync(A, total, A->rd_totals.p, sizeof(total), hipMemcpyDeviceToHost));
+    g_decode_counts[RD_CNT_D2H_BYTES] += sizeof(total);
+    // pass 2: the arrays
+    const size_t bytes[mgx_aligner::RD_H_N] = { (size_t)(n + 1) * 8, (size_t)total[RD_ALN] * sizeof(mgx_alignment), (size_t)total[RD_NODES] * 8,
+                                                (size_t)total[RD_CIGAR] * sizeof(mgx_cigar_op), (size_t)total[RD_SEQ], (size_t)n * 4,
+                                                (size_t)total[RD_LABELS] * 4 };
+    size_t all_bytes = 0;
+    for (size_t x : bytes) all_bytes += x;
+    auto no_buffer = [&](const char *which) {
+        return fail(MGX_ERR_OOM, "%s: the results of %llu queries need %llu bytes and no %s buffer of that size could be allocated", fn,
+                    (unsigned long long)n, (unsigned long long)all_bytes, which);
+    };
+    // (16 bytes more than needed: an array without elements still has an address)
+    if (A->rd_alns.ensure(bytes[mgx_aligner::RD_H_ALNS] + 16) != MGX_OK || A->rd_nodes.ensure(bytes[mgx_aligner::RD_H_NODES] + 16) != MGX_OK
+        || A->rd_cigar.ensure(bytes[mgx_aligner::RD_H_CIGAR] + 16) != MGX_OK || A->rd_seqs.ensure(bytes[mgx_aligner::RD_H_SEQS] + 16) != MGX_OK
+        || A->rd_labels.ensure(bytes[mgx_aligner::RD_H_LABELS] + 16) != MGX_OK)
+        return no_buffer("device");
+    b.alignments = A->rd_alns.as<RdAlignment>(); b.nodes = A->rd_nodes.as<uint64_t>(); b.cigar = A->rd_cigar.as<RdCigarOp>();
+    b.seqs = A->rd_seqs.as<char>(); b.labels = A->rd_labels.as<uint32_t>();
+    HIP_TRY((hipError_t)mgx_launch_decode_write(&b, A->hstream));
+    ++g_decode_counts[RD_CNT_WRITE];
+    const void *d_arrays[mgx_aligner::RD_H_N] = { d_begins + RD_ALN * stride, A->rd_alns.p, A->rd_nodes.p, A->rd_cigar.p, A->rd_seqs.p, A->rd_status.p,
+                                                  A->rd_labels.p };
+    const void *arrays[mgx_aligner::RD_H_N];
+    if (where == RD_TO_DEVICE) {
+        HIP_TRY(hipStreamSynchronize(A->hstream));       // (the arrays are complete when the call returns, whatever stream reads them)
+        for (int x = 0; x < mgx_aligner::RD_H_N; ++x) arrays[x] = d_arrays[x];
+    } else {
+        for (int x = 0; x < mgx_aligner::RD_H_N; ++x) {
+            if (bytes[x] + 1 > A->h_rd_bytes[x]) {
+                if (A->h_rd[x]) { (void)hipHostFree(A->h_rd[x]); A->h_rd[x] = nullptr; A->h_rd_bytes[x] = 0; }
+                const size_t want = bytes[x] + bytes[x] / 8 + 4096;
+                void *p = nullptr;
+                if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return no_buffer("pinned host"); }
+                A->h_rd[x] = p; A->h_rd_bytes[x] = want;
+            }
+            if (bytes[x]) HIP_TRY(hipMemcpyAsync(A->h_rd[x], d_arrays[x], bytes[x], hipMemcpyDeviceToHost, A->hstream));
+            g_decode_counts[RD_CNT_D2H_BYTES] += bytes[x];
+            arrays[x] = A->h_rd[x];
+        }
+        HIP_TRY(hipStreamSynchronize(A->hstream));
+    }
+    out->n_queries = n;
+    out->aln_begin = static_cast<const uint64_t *>(arrays[mgx_aligner::RD_H_ALN_BEGIN]);
+    out->alignments = static_cast<const mgx_alignment *>(arrays[mgx_aligner::RD_H_ALNS]);
+    out->nodes = static_cast<const uint64_t *>(arrays[mgx_aligner::RD_H_NODES]);
+    out->cigar = static_cast<const mgx_cigar_op *>(arrays[mgx_aligner::RD_H_CIGAR]);
+    out->seqs = static_cast<const char *>(arrays[mgx_aligner::RD_H_SEQS]);
+    out->status = static_cast<const int32_t *>(arrays[mgx_aligner::RD_H_STATUS]);
+    out->labels = total[RD_LABELS] ? static_cast<const uint32_t *>(arrays[mgx_aligner::RD_H_LABELS]) : nullptr;     // (as HostResults::view)
+    if (sizes) {
+        sizes->n_alignments = total[RD_ALN]; sizes->n_nodes = total[RD_NODES]; sizes->n_cigar = total[RD_CIGAR];
+        sizes->n_seq_bytes = total[RD_SEQ]; sizes->n_labels = total[RD_LABELS];
+    }
+    return MGX_OK;
+}
+
+int mgx_decode_results_device(mgx_aligner *A, mgx_results *out, mgx_results_sizes *sizes) {
+    if (!A || !out || !sizes) return fail(MGX_ERR_INVALID, "null argument");
+    const uint64_t n = A->n_reads;
+    memset(sizes, 0, sizeof(*sizes));
+    if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
+    const bool staged = n ? A->aligned_generation == A->stage_generation && A->last_d_seqs && A->last_d_offsets : A->aligned_empty;
+    if (!staged)
+        return fail(MGX_ERR_INVALID, "mgx_decode_results_device: no aligned batch on this handle, or another batch was staged after mgx_align_batch_device");
+    HIP_TRY(hipSetDevice(A->graph->device));
+    if (!n) {
+        // no query: aln_begin is its one zero, every other array is empty (and has an address)
+        if (int rc = A->rd_begins.ensure(64)) return rc;
+        HIP_TRY(hipMemsetAsync(A->rd_begins.p, 0, 64, A->hstream));
+        HIP_TRY(hipStreamSynchronize(A->hstream));
+        memset(out, 0, sizeof(*out));
+        out->aln_begin = A->rd_begins.as<uint64_t>();
+        out->alignments = reinterpret_cast<const mgx_alignment *>(A->rd_begins.as<uint64_t>() + 1);
+        out->nodes = A->rd_begins.as<uint64_t>() + 1;
+        out->cigar = reinterpret_cast<const mgx_cigar_op *>(A->rd_begins.as<uint64_t>() + 1);
+        out->seqs = reinterpret_cast<const char *>(A->rd_begins.as<uint64_t>() + 1);
+        out->status = reinterpret_cast<const int32_t *>(A->rd_begins.as<uint64_t>() + 1);
+        return MGX_OK;
+    }
+    return decode_on_device(A, RD_TO_DEVICE, out, sizes);
+}
+
 int mgx_fetch_results(mgx_aligner *A, mgx_results *out) {
     HostStageTimer t_fetch("fetch_results");
     const uint64_t n = A->n_reads;
     HIP_TRY(hipSetDevice(A->graph->device));
-    A->h_results.resize(n);
-    unsigned long long used = 0;
-    if (n) {
-        HIP_TRY(copy_sync(A, A->h_results.data(), A->results.p, n * sizeof(ReadResult), hipMemcpyDeviceToHost));
-        HIP_TRY(copy_sync(A, &used, cursor(A, CUR_OUT), 8, hipMemcpyDeviceToHost));
-        used = std::min<unsigned long long>(used, A->out_words);
-    }
-    A->h_stream.resize(used);
-    if (used) HIP_TRY(copy_sync(A, A->h_stream.data(), A->stream.p, used * 4, hipMemcpyDeviceToHost));
-    A->host.decode(A->h_results.data(), n, A->h_stream.data(), ~0ull, A->anno != nullptr);
-    A->host.view(out);
     // the aligned batch is read back below (post-chaining, the capacity retry): only while the staging buffers still hold it —
     // mgx_map_batch on this aligner re-stages them; a caller's device buffers are the caller's to keep until the fetch
     const bool batch_intact = A->aligned_generation == A->stage_generation && A->last_d_seqs && A->last_d_offsets;
+    if (A->opt.decode_on_device && n && batch_intact) {
+        // the option decode_on_device: the seven arrays come decoded (no records, no stream, no per-element work here)
+        A->h_results.clear();                            // (mgx_fetch_seed_info reads the records itself)
+        mgx_results_sizes sizes;
+        if (int rc = decode_on_device(A, RD_TO_HOST, out, &sizes)) return rc;
+        ++g_decode_counts[RD_CNT_FETCHES];
+        // the capacity retry tells a queue overflow (final) from an arena overflow by the record: the rare batch with a capacity
+        // status brings its records as well
+        if (std::find(out->status, out->status + n, (int32_t)MGX_ERR_CAPACITY) != out->status + n) {
+            A->h_results.resize(n);
+            HIP_TRY(copy_sync(A, A->h_results.data(), A->results.p, n * sizeof(ReadResult), hipMemcpyDeviceToHost));
+            g_decode_counts[RD_CNT_D2H_BYTES] += n * sizeof(ReadResult);
+        }
+    } else {
+        A->h_results.resize(n);
+        unsigned long long used = 0;
+        if (n) {
+            HIP_TRY(copy_sync(A, A->h_results.data(), A->results.p, n * sizeof(ReadResult), hipMemcpyDeviceToHost));
+            HIP_TRY(copy_sync(A, &used, cursor(A, CUR_OUT), 8, hipMemcpyDeviceToHost));
+            used = std::min<unsigned long long>(used, A->out_words);
+        }
+        A->h_stream.resize(used);
+        if (used) HIP_TRY(copy_sync(A, A->h_stream.data(), A->stream.p, used * 4, hipMemcpyDeviceToHost));
+        A->host.decode(A->h_results.data(), n, A->h_stream.data(), ~0ull, A->anno != nullptr);
+        A->host.view(out);
+    }
     if (A->cfg.post_chain_alignments && n) {
         // chain_alignments (dbg_aligner.cpp:328-332) on the host: needs the reads of the queries with two or more alignments once
         // more — one transfer of the span of the batch that holds them (none at all when no query has two)

@@ -375,6 +375,18 @@ class HipDBGAligner : public IDBGAligner {
         const std::vector<uint64_t> offsets = pack_headers(seq_batch, 0, seq_batch.size(), headers);
         return format_tsv(headers.data(), offsets.data(), seq_batch.size(), label_names);
     }
+    // The results of the batch align_batch_device ran last in the mgx_results layout, decoded on the device and left there
+    // (mgx_decode_results_device): every pointer of the view is DEVICE memory of the handle, valid until its next batch, fetch,
+    // decode or format call; *sizes (optional) receives the arrays' element counts.  Pre-retry (a capacity-status query has
+    // its status and no alignments) and, with post_chain_alignments, unchained.
+    mgx_results decode_batch_device(mgx_results_sizes *sizes = nullptr) const {
+        mgx_results res{};
+        mgx_results_sizes s{};
+        if (int rc = mgx_decode_results_device(a_, &res, &s))
+            throw std::runtime_error(std::string("mgx_decode_results_device: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
+        if (sizes) *sizes = s;
+        return res;
+    }
     // ... over reads that are in device memory already (HipReadParser::slice): n reads, offsets from 0
     void align_batch_device(const char *d_seqs, const uint64_t *d_offsets, uint64_t n) const {
         if (int rc = mgx_align_batch_device(a_, d_seqs, d_offsets, n, 1))
