@@ -10,9 +10,10 @@
 
 namespace mgx {
 
-// longest read a lane takes (packed strand in LDS: LANE_QWORDS words per lane).  The host lays the scratch out for 256; the kernel
-// is built twice (mgx_lane.hip): for reads of up to 256 characters, and — MGX_LANE_MAX_L=160 — for batches whose longest read has
-// at most 160, where the smaller packed strand is what lets a third wavefront per SIMD fit the LDS.
+// longest read a lane takes (packed strand in LDS: LANE_QWORDS words per lane).  The host lays the scratch out for 256, and the
+// kernel is built once (mgx_lane.hip), for reads of up to 256 characters.  (MGX_LANE_MAX_L remains as a build parameter: the second
+// build for batches whose longest read has at most 160 characters — a smaller packed strand, a third wavefront per SIMD — was
+// measured and not kept.)
 #ifndef MGX_LANE_MAX_L
 #define MGX_LANE_MAX_L 256
 #endif
