@@ -58,7 +58,7 @@
 #endif
 
 // PRIMARY graphs (DevConfig::canonical == 2, the CanonicalDBG wrapper of canon_graph.hpp) are compiled into separate
-// instantiations (-DMGX_WITH_PRIMARY=1: mgx_primary.hip for seeding, the mgx_grp.hip build that also carries alternative
+// instantiations (-DMGX_WITH_PRIMARY=1: that build of mgx_seed.hip for seeding, the mgx_grp.hip build that also carries alternative
 // paths for extension), so that the kernels every other graph runs on are the code they were without it.
 #ifndef MGX_WITH_PRIMARY
 #define MGX_WITH_PRIMARY 0
@@ -140,7 +140,7 @@ MGX_DEV int32_t iabs(int32_t a) { return a < 0 ? -a : a; }
 // ------------------------------------------------------------------------------------------------
 // Lanes per read of the extension kernel, which fixes the width of the chain path's register window and with it the
 // layout of the column slots in the arena.  The HIP build runs the extension with 8-lane groups only (mgx_grp.hip); the
-// host translation unit (mgx.hip, 64-lane seeding kernel) must compute the same arena layout, hence a constant that does
+// host driver (mgx.hip) and the 64-lane seeding kernel (mgx_seed.hip) must compute the same arena layout, hence a constant that does
 // not depend on the translation unit's own WAVE.  The host model runs every lane count.
 #if MGX_WAVE_EMU
 constexpr int32_t EXT_LANES = WAVE;
@@ -1892,7 +1892,7 @@ MGX_NI_G2 void make_seeder(Wave &w, int s) {
     SEED_T(5, tp)
 }
 
-#ifndef MGX_NO_EXTEND    // translation units that only seed (mgx.hip: k_map, k_seed) skip the extension half
+#ifndef MGX_NO_EXTEND    // translation units that only map or seed (mgx_map.hip, mgx_seed.hip, ...) skip the extension half
 // ------------------------------------------------------------------------------------------------
 // extension (DefaultColumnExtender::extend, A/aligner_extender_methods.cpp:412-772)
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // json_format.hpp — the text of `metagraph align --json` for an alignment batch (cli/align.cpp:287-305, Alignment::to_json and
-// path_json; restated by mgx_format_json in mgx.hip), from what mgx_align_batch_device leaves in device memory: the ReadResult
+// path_json; restated by mgx_format_json in mgx_text.hip), from what mgx_align_batch_device leaves in device memory: the ReadResult
 // records, the output stream (align_types.hpp:51-64, host_common.hpp:153-159) and the raw read bytes; plus the caller's headers.
 //
 // Written against the wave interface (wave.hpp): tests/test_json_format_model.py compiles this very file for the host

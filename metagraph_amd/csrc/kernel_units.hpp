@@ -1,7 +1,8 @@
 // kernel_units.hpp — what the translation units of libmgx.so call in one another: the launchers and build constants of the
-// kernel units (the host driver in mgx.hip launches them) and the library-internal accessors of mgx_annot.hip.  Declarations
-// only.  mgx.hip includes this file and so does every unit that defines one of these symbols, so that a signature which
-// drifts on one side is a compile error instead of a call through a wrong prototype.
+// kernel units (the host units launch them: the align pipeline in mgx.hip, mgx_map.hip, mgx_results.hip, mgx_text.hip) and the
+// library-internal accessors of mgx_annot.hip.  Declarations only.  Every unit that calls or defines one of these symbols includes
+// this file, so that a signature which drifts on one side is a compile error instead of a call through a wrong prototype.
+// (What the host units share among themselves — handles, error message, block pool — is host_state.hpp.)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -18,6 +19,11 @@ constexpr size_t MGX_PARSE_ARGS_BYTES = 144;            // sizeof(RpChunk), read
 constexpr size_t MGX_MAPFMT_ARGS_BYTES = 120;           // sizeof(MfBatch), map_format.hpp
 constexpr size_t MGX_JSONFMT_ARGS_BYTES = 120;          // sizeof(JfBatch), json_format.hpp
 constexpr size_t MGX_DECODE_ARGS_BYTES = 104;           // sizeof(RdBatch), results_decode.hpp
+constexpr unsigned MGX_SEED_STATIC_LDS_BYTES = 1792;    // static LDS of k_align<PH_SEED>, either build of mgx_seed.hip
+
+#ifndef MGX_SEL_ANCHOR_MAX
+#define MGX_SEL_ANCHOR_MAX 8192      // entries of the select-anchor table mgx_graph.hip builds (32 KB of LDS per workgroup of k_map_pipe, mgx_map.hip)
+#endif
 
 struct mgx_annotation;
 
@@ -51,8 +57,15 @@ unsigned mgx_lab64_static_lds(void);
 int mgx_lab64_waves_per_simd(void);
 int mgx_lab64_max_alt(void);
 
-// mgx_primary.hip: the seeding kernel with the CanonicalDBG branches; wps8 selects the 8-waves-per-SIMD instantiation
+// mgx_seed.hip: the wave-per-read seeding kernel (seed_kernel.hpp), two builds: the plain one and `_primary`
+// (-DMGX_WITH_PRIMARY=1: the CanonicalDBG branches, PRIMARY graphs).  params: AlignParams (host memory); blocks = wavefronts;
+// wps8 selects the 8-waves-per-SIMD instantiation.  static_lds: control block + sdust interval lists, rounded up to 128.
+// (The figure is the same in both builds, which each assert it: the host sizes the dynamic LDS of either from the plain one.)
+// mgx_seed_load: the plain build's code object onto the current device, without a launch (see load_map_kernels, host_state.hpp).
+int mgx_launch_seed(const void *params, uint32_t blocks, uint32_t lds_bytes, int wps8, void *stream);
 int mgx_launch_seed_primary(const void *params, uint32_t blocks, uint32_t lds_bytes, int wps8, void *stream);
+unsigned mgx_seed_static_lds(void);
+int mgx_seed_load(void);
 
 // mgx_lane.hip: the lane-per-read kernel.  d_params: LaneParams in DEVICE memory; blocks = resident wavefronts
 int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream);

@@ -180,7 +180,7 @@ __global__ void k_tuple_gather(const uint64_t *row_entry, const uint64_t *coord_
 }
 
 // every annotation object gets an id no other one of this process ever had: what is cached about an annotation elsewhere (the
-// per-graph "no dummy node's row holds a label" flag, mgx.hip) is keyed by it — pointers come back from malloc / hipMalloc after
+// per-graph "no dummy node's row holds a label" flag, mgx_graph.hip) is keyed by it — pointers come back from malloc / hipMalloc after
 // a destroy + create and would hand a new annotation the old one's entry
 static std::atomic<uint64_t> g_annotation_uid{0};
 

@@ -1,5 +1,5 @@
 // mgx_decode.hip — the structured results of an alignment batch (the mgx_results layout) on the device (results_decode.hpp; host
-// side: decode_on_device in mgx.hip, behind mgx_decode_results_device and the pipeline option decode_on_device).
+// side: decode_on_device in mgx_results.hip, behind mgx_decode_results_device and the pipeline option decode_on_device).
 //
 // Shapes.  k_decode_size: one query per lane (a serial walk over the headers of the query's few alignments: five sums), plus one
 // lane for the zeros that close the scans.  k_decode_write: one wavefront per query, four per 256-thread workgroup, grid-strided
@@ -13,7 +13,7 @@
 
 using namespace mgx;
 
-static_assert(sizeof(RdBatch) == MGX_DECODE_ARGS_BYTES, "RdBatch differs from what mgx.hip passes");
+static_assert(sizeof(RdBatch) == MGX_DECODE_ARGS_BYTES, "RdBatch differs from what mgx_results.hip passes");
 
 __global__ void __launch_bounds__(256) k_decode_size(RdBatch b) {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

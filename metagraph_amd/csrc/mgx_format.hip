@@ -1,4 +1,4 @@
-// mgx_format.hip — the TSV text of an alignment batch on the device (tsv_format.hpp; host side: mgx_format_tsv_batch in mgx.hip).
+// mgx_format.hip — the TSV text of an alignment batch on the device (tsv_format.hpp; host side: mgx_format_tsv_batch in mgx_text.hip).
 //
 // Shapes.  k_format_size: one query per lane (a serial walk over the query's few alignments; 4 bytes of arithmetic per CIGAR
 // run).  k_format_write: one wavefront per query, four per 256-thread workgroup, grid-strided — the text of a 150-bp read is
@@ -14,7 +14,7 @@
 
 using namespace mgx;
 
-static_assert(sizeof(TfBatch) == MGX_FORMAT_ARGS_BYTES, "TfBatch differs from what mgx.hip passes");
+static_assert(sizeof(TfBatch) == MGX_FORMAT_ARGS_BYTES, "TfBatch differs from what mgx_text.hip passes");
 
 __global__ void __launch_bounds__(256) k_format_size(TfBatch b) {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 // mgx_jsonfmt.hip — the text of `align --json` for a range of an alignment batch on the device (json_format.hpp; host side:
-// mgx_format_json_batch in mgx.hip).
+// mgx_format_json_batch in mgx_text.hip).
 //
 // Shapes.  k_jsonfmt_size and k_jsonfmt_write: one wavefront per query, four per 256-thread workgroup, grid-strided — both are
 // the one walk jf_line, which counts or stores (a line is ~60 bytes per path node, so a 150-bp read is a few thousand lane-sized
@@ -13,7 +13,7 @@
 
 using namespace mgx;
 
-static_assert(sizeof(JfBatch) == MGX_JSONFMT_ARGS_BYTES, "JfBatch differs from what mgx.hip passes");
+static_assert(sizeof(JfBatch) == MGX_JSONFMT_ARGS_BYTES, "JfBatch differs from what mgx_text.hip passes");
 
 __global__ void __launch_bounds__(256) k_jsonfmt_size(JfBatch b) {
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;

@@ -1,5 +1,5 @@
 // mgx_mapfmt.hip — the text of `align --map` for a whole batch on the device (map_format.hpp; host side: mgx_format_map_batch in
-// mgx.hip).
+// mgx_text.hip).
 //
 // Shapes.  k_mapfmt_size: NODES — one wavefront per query, four per 256-thread workgroup, grid-strided (the node array is read
 // 64 nodes at a time); the other formats — one query per lane.  k_mapfmt_write: one wavefront per query in the same grid
@@ -14,7 +14,7 @@
 
 using namespace mgx;
 
-static_assert(sizeof(MfBatch) == MGX_MAPFMT_ARGS_BYTES, "MfBatch differs from what mgx.hip passes");
+static_assert(sizeof(MfBatch) == MGX_MAPFMT_ARGS_BYTES, "MfBatch differs from what mgx_text.hip passes");
 
 __global__ void __launch_bounds__(256) k_mapfmt_size(MfBatch b) {
     if (b.format == MF_NODES) {

@@ -83,7 +83,7 @@ int mgx_launch_map_summary(const uint64_t *node_begin, const uint32_t *fwd, cons
 
 int mgx_launch_map_subk(const void *dev_graph, const char *seqs, const uint64_t *offsets, const uint64_t *node_begin, uint32_t *nodes,
                         uint64_t n_reads, uint32_t map_length, void *stream) {
-    static_assert(sizeof(DevGraph) == MGX_DEV_GRAPH_BYTES, "DevGraph differs from what mgx.hip passes");
+    static_assert(sizeof(DevGraph) == MGX_DEV_GRAPH_BYTES, "DevGraph differs from what mgx_map.hip passes");
     if (!n_reads) return 0;
     k_map_subk<<<(uint32_t)((n_reads + 3) / 4 < 16384 ? (n_reads + 3) / 4 : 16384), 256, 0, (hipStream_t)stream>>>(
         *static_cast<const DevGraph *>(dev_graph), seqs, offsets, node_begin, nodes, n_reads, (int32_t)map_length);

@@ -1,5 +1,5 @@
 // mgx_seedlane.hip — the lane-per-read seeding kernel (seed_lane.hpp): every lane of a wavefront seeds its own read, 64 reads
-// per instruction, in front of the wave-per-read seeder (k_align<PH_SEED>, mgx.hip).  A lane finishes a read completely
+// per instruction, in front of the wave-per-read seeder (k_align<PH_SEED>, mgx_seed.hip).  A lane finishes a read completely
 // (header, seeds, work key) or lists it for the wave program, which then seeds it from scratch.
 //
 // Shape: persistent wavefronts; a lane takes the next read of the batch as soon as it is through with its own (one atomic per

@@ -1,4 +1,4 @@
-// pack_swar.hpp — 32 bases -> 32 2-bit codes + 32 invalid flags without a per-base loop (k_pack_reads, mgx.hip).
+// pack_swar.hpp — 32 bases -> 32 2-bit codes + 32 invalid flags without a per-base loop (k_pack_reads, mgx_map.hip).
 // The same results as graph_build.hpp's pack_read_word() — KmerExtractorBOSS::encode (A C G T/U in either case = 0..3, anything else
 // invalid) and, for strand 1, the reverse complement — from the word's 32 bytes held as four 64-bit values: eight bases at a time.
 // tests/test_pack_swar.py compiles this header for the host and compares it with the byte loop on random and adversarial bytes.

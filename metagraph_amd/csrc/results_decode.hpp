@@ -20,7 +20,7 @@
 
 namespace mgx {
 
-// mgx_cigar_op and mgx_alignment as the device writes them (mgx.hip asserts sizes and offsets against include/mgx.h)
+// mgx_cigar_op and mgx_alignment as the device writes them (mgx_results.hip asserts sizes and offsets against include/mgx.h)
 struct RdCigarOp { uint32_t len; uint8_t op; uint8_t pad[3]; };
 struct RdAlignment {
     int32_t score;

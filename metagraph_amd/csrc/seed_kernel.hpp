@@ -1,5 +1,5 @@
-// seed_kernel.hpp — the wave-per-read kernel around align_read (one 64-lane wavefront per read), instantiated for the
-// seeding phase by mgx.hip (every graph but PRIMARY ones) and by mgx_primary.hip (-DMGX_WITH_PRIMARY=1).
+// seed_kernel.hpp — the wave-per-read kernel around align_read (one 64-lane wavefront per read), instantiated for the seeding
+// phase by the two builds of mgx_seed.hip (plain: every graph but PRIMARY ones; -DMGX_WITH_PRIMARY=1) and for extension by mgx_ext64.hip.
 #pragma once
 #include "align_core.hpp"
 

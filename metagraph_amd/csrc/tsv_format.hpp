@@ -1,4 +1,4 @@
-// tsv_format.hpp — the TSV text of an alignment batch (cli/align.cpp:262-285, restated by mgx_format_tsv_labeled in mgx.hip),
+// tsv_format.hpp — the TSV text of an alignment batch (cli/align.cpp:262-285, restated by mgx_format_tsv_labeled in mgx_text.hip),
 // from what mgx_align_batch_device leaves in device memory: the ReadResult records, the output stream (align_types.hpp:51-64,
 // host_common.hpp:153-159) and the raw read bytes; plus the headers and the label names the caller hands over.
 //

@@ -158,14 +158,14 @@ void *emu_graph_create(const mgx_boss_view *view) {
     G->terminus.assign(G->mode == MGX_MODE_PRIMARY ? (size_t)n_blocks * 3 + (G->tables ? (n_nodes + 2) / 2 + 1 : 0) : (size_t)n_blocks, 0);
     g.terminus = G->terminus.data();
     if (G->mode == MGX_MODE_PRIMARY) {
-        // the wrapper's degrees (as k_terminus_primary in mgx.hip)
+        // the wrapper's degrees (as k_terminus_primary in mgx_graph.hip)
         for (uint64_t v = 1; v <= n; ++v) {
             if (!in_graph(g, v)) continue;
             const uint32_t t = build_terminus_primary(g, v);
             if (t & 1) G->terminus[v >> 6] |= 1ull << (v & 63);
             if (t & 2) G->terminus[n_blocks + (v >> 6)] |= 1ull << (v & 63);
         }
-        if (G->tables) {                                       // as k_primary_tables in mgx.hip
+        if (G->tables) {                                       // as k_primary_tables in mgx_graph.hip
             uint32_t *rcn = reinterpret_cast<uint32_t *>(G->terminus.data() + 3ull * n_blocks);
             for (uint64_t e = 1; e <= n; ++e) {
                 if (build_pal_bit(g, e)) G->terminus[2ull * n_blocks + (e >> 6)] |= 1ull << (e & 63);

@@ -172,7 +172,7 @@ def read_lengths_and_invalid_characters_at_word_edges(backend, k):
 # ---------------------------------------------------------------------------------------------------------------------------
 # c. the index at size: select-anchor shifts 7 and 8
 # ---------------------------------------------------------------------------------------------------------------------------
-SEL_ANCHOR_MAX = 8192            # MGX_SEL_ANCHOR_MAX (mgx.hip): entries of the select-anchor table k_map_pipe copies to LDS
+SEL_ANCHOR_MAX = 8192            # MGX_SEL_ANCHOR_MAX (kernel_units.hpp): entries of the select-anchor table k_map_pipe copies to LDS
 
 
 def sel_anchor_shift(total_last):
