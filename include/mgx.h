@@ -742,6 +742,20 @@ void mgx_boss_file_free(mgx_boss_file *f);
 int mgx_edgemask_read(const char *path, uint32_t state, uint64_t n_edges, uint8_t *valid_out);
 /* mgx_boss_file_read + mgx_graph_create: DBGSuccinct::load for the device */
 int mgx_graph_load_dbg(const char *path, int device, mgx_graph **out);
+/* mgx_graph_load_dbg with the payloads decoded by kernels: same contract, same graph, same error codes, and a
+ * malformed file's message names the same field.  The host reads the file and walks the container headers (sizes, widths, the
+ * tree's <= 511 nodes, F, k, state, mode); the rrr_vector<63> blocks, the wavelet tree of W, the int_vector of FAST-state graphs
+ * and `last` (rrr, bit_vector_stat or sd_vector) go to the device as they stand in the file and are decoded there into the
+ * W / last byte arrays, which mgx_graph_create takes with on_device = 1 and which are released on return.  Nothing of W or last
+ * is copied back to the host.  Refused as by the host reader: DYN state, bit_vector_il.  (A wavelet tree whose node table is
+ * not a tree, which no writer produces, is decoded by the host reader and uploaded.) */
+int mgx_graph_load_dbg_device(const char *path, int device, mgx_graph **out);
+/* Test hook: the same kernels, then W / last copied back into a host-owned mgx_boss_file (mgx_boss_file_free) — what
+ * mgx_boss_file_read returns, byte for byte.  Like it, and unlike the two load calls, it accepts any alphabet. */
+int mgx_boss_file_decode_device(const char *path, int device, mgx_boss_file *out);
+/* Test hook: out4 = launches of the rrr kernels, launches of the wavelet-tree / unpack / last kernels, bytes copied
+ * host-to-device, bytes copied device-to-host by the two calls above — since the library was loaded. */
+void mgx_dbg_decode_kernel_launch_counts(uint64_t *out4);
 
 typedef struct mgx_column_file mgx_column_file;
 /* One or several `.column.annodbg` files over the same rows, their columns side by side in argument order (merge_load;

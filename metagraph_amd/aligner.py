@@ -29,11 +29,15 @@ def pack_queries(queries):
     return b"".join(bs), offs
 
 
-def read_boss_file(path, arrays=True):
-    """mgx_boss_file_read (host only, no GPU): k, sigma, mode, state, n_edges, F and — with arrays — W / last of a `.dbg` file."""
+def read_boss_file(path, arrays=True, on_device=False, device=0):
+    """mgx_boss_file_read (host only, no GPU): k, sigma, mode, state, n_edges, F and — with arrays — W / last of a `.dbg` file.
+    on_device: mgx_boss_file_decode_device, the same content decoded by the kernels of mgx_graph_load_dbg_device and copied back."""
     L = capi.lib()
     f = capi.BossFile()
-    _check(L.mgx_boss_file_read(str(path).encode(), C.byref(f)))
+    if on_device:
+        _check(L.mgx_boss_file_decode_device(str(path).encode(), device, C.byref(f)))
+    else:
+        _check(L.mgx_boss_file_read(str(path).encode(), C.byref(f)))
     try:
         out = {"k": f.k, "sigma": f.sigma, "mode": f.mode, "state": f.state, "n_edges": f.n_edges, "F": [int(f.F[i]) for i in range(f.sigma)]}
         if arrays:
@@ -97,11 +101,13 @@ class Graph:
         self.n_edges = v.n_edges
 
     @classmethod
-    def load(cls, path, device=0):
-        """mgx_graph_load_dbg: a `.dbg` file written by the reference (DBGSuccinct::load, dbg_succinct.cpp:690-785)."""
+    def load(cls, path, device=0, on_device=False):
+        """mgx_graph_load_dbg: a `.dbg` file written by the reference (DBGSuccinct::load, dbg_succinct.cpp:690-785).
+        on_device: mgx_graph_load_dbg_device, the file's payloads decoded by kernels (the same graph)."""
         self = cls.__new__(cls)
         self.h = C.c_void_p()
-        _check(capi.lib().mgx_graph_load_dbg(str(path).encode(), device, C.byref(self.h)))
+        load = capi.lib().mgx_graph_load_dbg_device if on_device else capi.lib().mgx_graph_load_dbg
+        _check(load(str(path).encode(), device, C.byref(self.h)))
         self.k = capi.lib().mgx_graph_k(self.h)
         self.n_edges, self.mode = capi.lib().mgx_graph_num_edges(self.h), capi.lib().mgx_graph_mode(self.h)
         return self

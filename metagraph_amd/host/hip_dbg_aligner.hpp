@@ -129,6 +129,12 @@ class HipBOSSGraph {
         v.mode = mode; v.on_device = 0;          // DeBruijnGraph::get_mode(); PRIMARY graphs are aligned through CanonicalDBG
         if (int rc = mgx_graph_create(&v, device, &g_)) throw std::runtime_error(std::string("mgx_graph_create: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
     }
+    // a `.dbg` file written by the reference (DBGSuccinct::load); load_on_device: its payloads are decoded by kernels
+    // (mgx_graph_load_dbg_device) instead of on this thread — the same graph
+    explicit HipBOSSGraph(const std::string &dbg_path, int device = 0, bool load_on_device = false) {
+        const int rc = load_on_device ? mgx_graph_load_dbg_device(dbg_path.c_str(), device, &g_) : mgx_graph_load_dbg(dbg_path.c_str(), device, &g_);
+        if (rc) throw std::runtime_error(std::string(mgx_last_error()) + " (" + std::to_string(rc) + ")");
+    }
     ~HipBOSSGraph() { mgx_graph_destroy(g_); }
     HipBOSSGraph(const HipBOSSGraph &) = delete;
     size_t get_k() const { return mgx_graph_k(g_); }
@@ -147,6 +153,10 @@ class HipGraphSet {
                 const uint8_t *valid = nullptr, uint32_t mode = MGX_MODE_BASIC) {
         if (n_devices < 1) throw std::runtime_error("HipGraphSet: at least one device");
         for (int d = 0; d < n_devices; ++d) replicas_.emplace_back(new HipBOSSGraph(k, n_edges, W, last, F, valid, d, mode));
+    }
+    HipGraphSet(int n_devices, const std::string &dbg_path, bool load_on_device = false) {
+        if (n_devices < 1) throw std::runtime_error("HipGraphSet: at least one device");
+        for (int d = 0; d < n_devices; ++d) replicas_.emplace_back(new HipBOSSGraph(dbg_path, d, load_on_device));
     }
     size_t size() const { return replicas_.size(); }
     static size_t device_of_worker(size_t worker, size_t n_devices) { return worker % n_devices; }

@@ -39,6 +39,9 @@
 //                             keeps it).  Files outside the grammar: exit status 1 and the byte position.  Not with --map or
 //                             --rccl-gather (--map has --map-on-device, below, which takes --parse-on-device without
 //                             --format-on-device)
+//             [--load-on-device]  GRAPH.dbg is decoded by kernels (mgx_graph_load_dbg_device): the host walks the file's headers, the
+//                             rrr blocks, the wavelet tree of W and `last` are decoded on the device.  The same graph, the same
+//                             output; the default decodes on the host (mgx_boss_file_read)
 //             [--devices D]   in-process multi-GPU: one graph replica per device, whole batches routed round-robin, no collective
 //             [--rccl-gather] with --devices D: one worker per device, batches in rounds of D; every round's device results are
 //                             gathered to device 0 over RCCL (mgx_gather_*: the C-ABI of north_star's "RCCL-over-xGMI only to
@@ -108,7 +111,28 @@ int main(int argc, char **argv) {
     uint64_t hdr[7];
     std::vector<uint8_t> W, last;
     uint32_t graph_mode = MGX_MODE_BASIC;
-    if (ends_with(argv[1], ".dbg")) {             // DBGSuccinct::load (dbg_succinct.cpp:690-711)
+    std::unique_ptr<HipGraphSet> loaded;           // --load-on-device: the replicas, made here (k comes from them)
+    bool load_on_device = false;
+    int load_devices = 1;
+    for (int i = 3; i < argc; ++i) {
+        if (!strcmp(argv[i], "--load-on-device")) load_on_device = true;
+        else if (!strcmp(argv[i], "--devices") && i + 1 < argc) load_devices = std::max(1, atoi(argv[++i]));
+    }
+    if (load_on_device) {
+        if (!ends_with(argv[1], ".dbg")) { fprintf(stderr, "error: --load-on-device decodes a `.dbg` file on the device: %s is none\n", argv[1]); return 1; }
+        if (load_devices > mgx_device_count() && mgx_device_count() > 0) {
+            fprintf(stderr, "error: --devices %d but %d HIP device(s) visible\n", load_devices, mgx_device_count());
+            return 1;
+        }
+        try {
+            loaded.reset(new HipGraphSet(load_devices, argv[1], true));
+        } catch (const std::exception &e) {
+            fprintf(stderr, "error: %s\n", e.what());
+            return 1;
+        }
+        hdr[0] = loaded->for_worker(0).get_k();
+        hdr[1] = mgx_graph_num_edges(loaded->for_worker(0).handle());
+    } else if (ends_with(argv[1], ".dbg")) {      // DBGSuccinct::load (dbg_succinct.cpp:690-711)
         mgx_boss_file f;
         if (mgx_boss_file_read(argv[1], &f) != MGX_OK) { fprintf(stderr, "error: %s\n", mgx_last_error()); return 1; }
         if (f.sigma != 5) { fprintf(stderr, "error: %s: alphabet of %u characters; DNA graphs only\n", argv[1], f.sigma); mgx_boss_file_free(&f); return 1; }
@@ -224,7 +248,8 @@ int main(int argc, char **argv) {
             fprintf(stderr, "error: --devices %d but %d HIP device(s) visible\n", devices, mgx_device_count());
             return 1;
         }
-        HipGraphSet graphs(devices, k, n, W.data(), last.data(), hdr + 2, nullptr, graph_mode);
+        if (!loaded) loaded.reset(new HipGraphSet(devices, k, n, W.data(), last.data(), hdr + 2, nullptr, graph_mode));
+        HipGraphSet &graphs = *loaded;
         std::unique_ptr<HipAnnotation> annotation;
         std::vector<std::string> label_names;
         if (!anno_paths.empty() && devices != 1) { fprintf(stderr, "error: -a with --devices 1 only (one annotation replica)\n"); return 1; }
