@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
+#define MGX_ABI_VERSION 6      /* still 6: mgx_stats::n_lane_exact_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
+                                * header) and the option exact; before that, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
                                 * (the mgx_results layout of a batch, written by kernels); before that mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
                                 * batch, written by kernels); before that mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
                                 * `align --map`, written by kernels); before that mgx_read_parser_* / mgx_parse_reads / mgx_parse_kernel_launch_counts (FASTA / FASTQ text to
@@ -212,8 +213,8 @@ typedef struct mgx_stats {
     uint64_t n_rank_lines;      /* 64-B block reads issued for rank_W / W / last        */
     uint64_t n_select_lines;    /* 64-B block reads issued for select_last / select_W  */
     uint64_t n_bit_lines;       /* side-table reads (MEM terminus bits, first chars)   */
-    uint64_t n_columns;         /* DP columns computed                                  */
-    uint64_t n_extensions;      /* DefaultColumnExtender::extend calls                  */
+    uint64_t n_columns;         /* DP columns computed (none for a read of n_lane_exact_reads) */
+    uint64_t n_extensions;      /* DefaultColumnExtender::extend calls (none for a read of n_lane_exact_reads: no DP ran) */
     uint64_t n_seeds;
     uint64_t n_map_lines;       /* part of n_rank_lines + n_select_lines issued by the k-mer mapping kernel */
     uint64_t n_capacity_errors; /* reads whose status is MGX_ERR_CAPACITY */
@@ -222,8 +223,8 @@ typedef struct mgx_stats {
     uint64_t extend_cycles[8];  /* extend() breakdown: pop, stage+band, outgoing, column, scan, commit, conv, push */
     double seed_kernel_ms, align_kernel_ms;   /* HIP-event time of the k-mer mapping kernel and of the whole
                                                  alignment stage (seeding + sort + extension), last batch */
-    double seeding_ms, sort_ms, extend_ms;    /* split pipeline only (0 otherwise): seeding kernel, work sort,
-                                                 extension kernel */
+    double seeding_ms, sort_ms, extend_ms;    /* split pipeline only (0 otherwise): seeding kernel, work sort (with the lane
+                                                 kernel's exact exit, k_lane_exact, which runs in front of it), extension kernel */
     uint64_t n_seed_lines;      /* split pipeline: part of the line counters issued by the seeding kernel */
     uint64_t n_fast_columns;    /* part of n_columns computed by the register-resident chain path */
     uint64_t extend_kernels;    /* which extension kernels the last batch launched (MGX_KERNEL_* bits): what a parity test
@@ -244,6 +245,9 @@ typedef struct mgx_stats {
     double seed_lane_ms;        /* HIP-event time of the lane-per-read seeder (part of seeding_ms) */
     uint64_t seed_lane_left_reads[16]; /* reads it left to the seeding kernel, by reason (seed_lane.hpp: 1 read length, 2 k-mer positions,
                                    3 characters outside ACGT, 4 the DUST scan could mask something, 5 alternative nodes, 6 / 7 seeds) */
+    uint64_t n_lane_exact_reads; /* part of n_lane_reads: reads finished through the lane kernel's exact exit (k_lane_exact, csrc/lane_read.hpp
+                                   lane_exact(): the first seed of the strand aligned first spans the query, so the result is the all-match
+                                   alignment over the seed's nodes and no DP runs; n_lane_reads + sum(lane_bail_reads) == reads still holds) */
 } mgx_stats;
 enum { MGX_KERNEL_GRP8 = 1, MGX_KERNEL_GRP8_PRIM = 2, MGX_KERNEL_GRP8_ALT = 4, MGX_KERNEL_EXT64 = 8, MGX_KERNEL_LANE = 16,
        MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64 /* the label-aware builds of the 64-lane and the 8-lane kernel */ };
@@ -400,6 +404,9 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   groups_per_wave=n    8-lane kernel: n = 1 .. 8 groups of a wavefront take reads, 0 = all (default: from the batch size)
  *   multi_pass=0|1       one extension per read and launch (default: automatic from the seeds per read)
  *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic)
+ *   exact=0|1            the lane kernel's exact exit: reads whose first seed spans the query are finished in closed form, without
+ *                        DP (default: automatic — on for the batches the lane kernel takes of its own accord; 1: wherever the lane
+ *                        kernel runs and the configuration allows it; never for label-aware batches)
  *   device_share=n       n handles are at work on this device at the same time (worker threads): this handle sizes its per-slot
  *                        arenas for 1 / n of the machine (default 1: all of it)
  *   seed_lane=0|1        the lane-per-read seeder in front of the seeding kernel (default: automatic)

@@ -60,7 +60,7 @@ struct ReadResult {
                              // each as 6 words (score, offset, n_nodes, n_cigar, seq_len, orientation) + the same arrays
     // intermediate products for parity tests
     uint32_t num_matches_fwd, num_matches_rc, n_seeds_fwd, n_seeds_rc;
-    uint32_t n_extensions, n_columns;
+    uint32_t n_extensions, n_columns;    // (both 0 for a read the lane kernel's exact exit finished: no DP ran, lane_read.hpp lane_exact())
 };
 
 struct DevSeed {             // Seed (alignment.hpp:32-98); full seeds reference the strand's node array

@@ -254,7 +254,9 @@ MGX_DEV int lane_children(const DevGraph &g, uint32_t vv, uint32_t sel_r, uint32
 // where the alignment lane_emit() writes out lives: the column slots of the (only) extension, walked down the parent links; the
 // path arrays the forward alignment was moved to when a backward pass followed; or the slots of the backward extension, whose
 // reversal (Alignment::reverse_complement) is what a walk down the parent links yields anyway
-enum { LANE_EMIT_SLOTS = 0, LANE_EMIT_ARRAYS = 1, LANE_EMIT_SLOTS_REVERSED = 2 };
+// ... or nowhere: LANE_EMIT_EXACT, the closed form of a read whose first seed spans the query (lane_exact() below) — the strand's
+// own nodes from the mapping kernel's array, one CIGAR run "L=", the strand's characters
+enum { LANE_EMIT_SLOTS = 0, LANE_EMIT_ARRAYS = 1, LANE_EMIT_SLOTS_REVERSED = 2, LANE_EMIT_EXACT = 3 };
 
 // ---- the wavefront's scratch as one lane sees it (layout: LaneParams, lane_types.hpp) ----
 // `il`: the interleaved part from this lane's word on (wave base + 4 * lane): word w of column c's slot, of its S row
@@ -368,8 +370,8 @@ struct LaneResult {
 #define f_idx LANE_CI(CD_F_IDX)
 #define f_max_val LANE_CI(CD_F_MAX)
 // pass: 0 = a new read; 1 = the backward pass of the read whose call with pass 0 returned LR_AGAIN (same lane, nothing in between).
-MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, const int pass, uint8_t *scratch, const LaneChip &chip,
-                      LaneCounters &ctr, LaneResult &R) {
+MGX_DEV int lane_read_dp(const LaneParams &LP, uint64_t read, const uint32_t item, const int pass, uint8_t *scratch, const LaneChip &chip,
+                         LaneCounters &ctr, LaneResult &R) {
     const AlignParams &P = LP.P;
     const DevConfig &cfg = P.cfg;
     const DevLimits &lim = P.lim;
@@ -1390,10 +1392,69 @@ MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, 
 #undef f_idx
 #undef f_max_val
 
+// ---- the exact exit (LaneParams::exact) ----
+// A read whose first seed — of the strand aligned first — spans the query (clipping 0, length L, offset 0: every k-mer of the
+// strand is a node) needs no DP.  aln_both extends this seed first (dbg_aligner.cpp:670-675); extend() replays it from a root
+// with left_end_bonus (aligner_extender_methods.cpp:443-470) and its queue pops the all-match column first at every query
+// position (mismatches < m, gaps < 0: lane_exact_config), so it reaches the query's end before any cap, x-drop or side branch
+// matters; backtrack starts from the best cell of the columns with offset >= L - 1 (:811, :856), the last cell of that path with
+// right_end_bonus; the alignment has clipping 0, so no backward pass follows (dbg_aligner.cpp:690); whatever the later seeds yield
+// scores lower and the aggregator keeps one alignment.  No alignment of the query scores above m L + left_end_bonus +
+// right_end_bonus, and only this one reaches it.  The score must pass min_path_score and min_cell_score (backtrack's
+// min_start_score, aln_both's threshold): a read whose full score does not runs the DP as ever, as does every read that
+// lane_read_dp() would turn away before it looks at its first seed (length, header status, a second strand to align).
+// Returns whether R is filled (as lane_read_dp() fills it for LR_DONE; no extension ran: n_extensions = n_columns = 0).
+MGX_DEV bool lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R) {
+    const AlignParams &P = LP.P;
+    const DevConfig &cfg = P.cfg;
+    if (P.labeled) return false;
+    const int32_t k = (int32_t)P.g.k;
+    const int32_t L = (int32_t)(gld(P.offsets + read + 1) - gld(P.offsets + read));
+    if (L > (int32_t)P.lim.Lmax || L > LANE_MAX_L || L < k) return false;
+    const SeedHdr *hp = P.seed_hdr + read;
+    if (gld(&hp->status) != ST_OK) return false;
+    const uint32_t nm0 = gld(&hp->num_matching[0]), nm1 = gld(&hp->num_matching[1]);
+    const int32_t ns0 = (int32_t)gld(&hp->n_seeds[0]), ns1 = (int32_t)gld(&hp->n_seeds[1]);
+    const bool have_rc = cfg.fwd_and_rc != 0;
+    // align_both_directions (:738-755), as lane_read_dp(): the strand with more matches; a second strand to align is not for here
+    const int first = nm0 >= nm1 ? 0 : 1;
+    const int s = have_rc ? first : 0;
+    if (have_rc) {
+        const uint32_t m_first = first ? nm1 : nm0, m_second = first ? nm0 : nm1;
+        const int32_t n_second = first ? ns0 : ns1;
+        if ((double)m_second >= (double)m_first * cfg.rel_score_cutoff && n_second > 0) return false;
+    }
+    if ((s ? ns1 : ns0) <= 0) return false;
+    const DevSeed *s0 = P.seed_stream + gld(&hp->off) + (s ? ns0 : 0);
+    if (!(gld(&s0->clipping) == 0 && (int32_t)gld(&s0->length) == L && gld(&s0->offset) == 0)) return false;
+    const int32_t full = LP.self_score * L + cfg.left_end_bonus + cfg.right_end_bonus;
+    if (full < cfg.min_path_score || full < cfg.min_cell_score) return false;
+    ReadResult &rr = R.rr;
+    rr.status = ST_OK; rr.n_alignments = 0; rr.score = 0; rr.offset = 0; rr.n_nodes = rr.n_cigar = rr.seq_len = 0;
+    rr.orientation = 0; rr.stream_off = 0;
+    rr.num_matches_fwd = nm0; rr.num_matches_rc = nm1; rr.n_seeds_fwd = (uint32_t)ns0; rr.n_seeds_rc = (uint32_t)ns1;
+    rr.n_extensions = 0; rr.n_columns = 0;
+    R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0; R.label = 0;
+    R.score = full; R.offset = 0; R.clip = 0; R.end_clip = 0; R.n_runs = 1; R.j_hi = 0; R.n_nodes = L - k + 1; R.n_seq = L;
+    R.words = (uint32_t)R.n_nodes + 1u + ((uint32_t)L + 3) / 4;
+    return true;
+}
+
+// One read, as the host model calls it: the exact exit where it is on, else the DP.  (On the device the two are two kernels,
+// mgx_lane.hip: k_lane_exact runs lane_exact() on every read before the work sort, k_lane runs lane_read_dp() on the others.)
+MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, const int pass, uint8_t *scratch, const LaneChip &chip,
+                      LaneCounters &ctr, LaneResult &R) {
+    if (!pass && LP.exact && lane_exact(LP, read, R)) return LR_DONE;
+    return lane_read_dp(LP, read, item, pass, scratch, chip, ctr, R);
+}
+
 // flat_read_end: the aggregator's one alignment -> output stream at word `so` (R.words of them, handed out by the caller: one
 // atomic per wavefront on the device), the result record, the seed dump of the test hook
-MGX_DEV void lane_emit(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
-                       const uint64_t so) {
+// WITH_EXACT: R may be what lane_exact() left (the kernel writes those reads apart, and keeps the closed form's code out of the
+// path behind the DP: k_lane has no register to spare, mgx_lane.hip)
+template <bool WITH_EXACT>
+MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
+                         const uint64_t so) {
     const AlignParams &P = LP.P;
     const uint8_t *slots = scratch;                      // (lane_slot_word)
     ReadResult &rr = R.rr;
@@ -1417,6 +1478,23 @@ MGX_DEV void lane_emit(const LaneParams &LP, const uint64_t read, const uint8_t 
                     gst(dseq + x, decode_code((geom >> 24) & 7u));
                     if ((int32_t)(link >> 16) >= k_minus_1) { if (ni >= 0) gst(dst + ni, node); --ni; }
                     j = (int32_t)(link & 0xFFFFu);
+                }
+            } else if (WITH_EXACT && R.mode == LANE_EMIT_EXACT) {
+                // the closed form: the strand's nodes as the mapping kernel left them, "L=", the strand's characters (four to a word,
+                // the last one padded with zeros)
+                const uint64_t off = gld(P.offsets + read);
+                const uint32_t *rn = (R.strand ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
+                const uint64_t *pw = LP.pk[R.strand] + packed_word_begin(off, read);
+                for (int32_t x = 0; x < R.n_nodes; ++x) gst(dst + x, gld(rn + x));
+                gst(dst + R.n_nodes + nc++, ((uint32_t)R.n_seq << 3) | OP_MATCH);
+                uint32_t *dw = dst + R.n_nodes + n_cigar;
+                uint64_t qw = 0;
+                for (int32_t x = 0; x < R.n_seq; x += 4) {
+                    if (!(x & 31)) qw = gld(pw + (x >> 5));
+                    uint32_t v = 0;
+                    for (int t = 0; t < 4; ++t)
+                        if (x + t < R.n_seq) v |= (uint32_t)decode_code(((uint32_t)(qw >> (2 * ((x + t) & 31))) & 3u) + 1u) << (8 * t);
+                    gst(dw + (x >> 2), v);
                 }
             } else if (R.mode == LANE_EMIT_ARRAYS) {
                 // the forward alignment as the backward pass kept it: path order, runs last first
@@ -1474,6 +1552,11 @@ MGX_DEV void lane_emit(const LaneParams &LP, const uint64_t read, const uint8_t 
             }
         }
     }
+}
+
+MGX_DEV void lane_emit(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
+                       const uint64_t so) {
+    lane_emit_t<true>(LP, read, scratch, chip, R, so);
 }
 
 } // namespace mgx

@@ -2,6 +2,7 @@
 // parameters, its scratch layout and the test of whether a batch's configuration is one the kernel takes at all.
 #pragma once
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/mgx.h"
@@ -54,8 +55,16 @@ struct LaneParams {
     uint32_t *bail_list;                 // reads for the group kernel, in processing order
     unsigned long long *bail_count;
     unsigned long long *done_count;
-    unsigned long long *bail_hist;       // [32] reads passed on, by the LANE_BAIL code of the test that sent them (lane_read.hpp)
+    unsigned long long *bail_hist;       // [32] reads passed on, by the LANE_BAIL code of the test that sent them (lane_read.hpp);
+                                         // [LANE_HIST_EXACT] reads finished through the exact exit (part of *done_count, which is
+                                         // what the host reads; the word is there for probes of a launch's counters)
+    // (behind what k_lane reads, whose offsets stay what they were)
+    uint32_t exact;                      // 1: a read whose first seed spans the query is finished without DP (lane_read.hpp, the exact
+                                         // exit; only where lane_exact_config() holds).  0 by default: every read runs its columns
+    uint32_t done_key;                   // exact, on the device: the work key k_lane_exact gives the reads it finished — above every
+                                         // key of the seeding phase, so that the work sort puts them behind the items k_lane is launched on
 };
+constexpr int LANE_HIST_EXACT = 48;        // (bail_hist has 64 words; [32 .. 41] are the section timers of -DMGX_LANE_TIMERS builds)
 
 // columns of an extension along one path: the root, one per query character, the deletions past the query's end that the x-drop
 // still allows, the spare slot of the `size >= capacity - 1` test (a read that needs more goes to the group kernel)
@@ -78,6 +87,30 @@ inline uint64_t lane_wave_scratch_bytes(uint32_t max_cols, uint64_t rest_stride)
     return lane_slots_bytes(max_cols) + lane_s8_bytes(max_cols) + lane_runs_bytes() + (uint64_t)LANE_WAVE * rest_stride;
 }
 
+
+// Whether the exact exit (lane_read.hpp lane_exact(), mgx_lane.hip k_lane_exact) may be on, given that lane_enabled() holds: the conditions, beyond lane_enabled()'s, under
+// which a read whose first seed spans the query has the all-match alignment over the seed's nodes as its one result, with the score
+// m L + left_end_bonus + right_end_bonus (DESIGN.md 3.4 "the exact exit").  What depends on the read's length — min_path_score
+// and min_cell_score against that score — is tested per read in lane_exact().
+//  - every mismatch scores strictly below a match and a gap strictly below 0: no second alignment reaches the full score, and at a
+//    fork the all-match child is the only top of the extender's queue (no tie for the order of equal columns to resolve);
+//  - right_end_bonus >= 0: an alignment that stops short of the query's end cannot score above the full one;
+//  - xdrop >= 0: the cell that holds the best score so far never falls under the x-drop cut-off;
+//  - max_nodes_per_seq_char and max_ram_per_alignment need no condition: extend() tests them only for a column whose maximum is
+//    below the best score so far (aligner_extender_methods.cpp:521-547), which the all-match head never is;
+//  - not label-aware (the one-label bookkeeping of the lane reads rows column by column).
+inline bool lane_exact_config(const mgx_config &c, const DevConfig &d, uint32_t labeled_flags) {
+    if (labeled_flags & 1u) return false;
+    const char acgt[4] = { 'A', 'C', 'G', 'T' };
+    const int m = c.score_matrix[(int)'A'][(int)'A'];
+    for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y)
+            if (x != y && c.score_matrix[(int)acgt[x]][(int)acgt[y]] >= m) return false;
+    if (c.gap_opening_penalty >= 0) return false;
+    if (c.right_end_bonus < 0 || d.right_end_bonus < 0) return false;
+    if (c.xdrop < 0) return false;
+    return true;
+}
 
 // Whether the lane-per-read kernel may run in front of the group kernel for this configuration (every read it cannot finish
 // goes to the group kernel anyway; this only rules out configurations in which its shortcuts would not be exact or no read
@@ -110,6 +143,10 @@ inline bool lane_enabled(const mgx_config &c, const DevConfig &d, uint32_t k, ui
     if (c.left_end_bonus < 0) return no("negative left end bonus");
     if (!(c.rel_score_cutoff >= 0.0 && c.rel_score_cutoff <= 1.0)) return no("rel_score_cutoff outside [0, 1]");
     LP->self_score = m;
+    // (the host model: MGX_EMU_LANE_EXACT=1 sets the exact exit where the configuration allows it; the product's plan_lane()
+    // decides by its own rule and overwrites this)
+    const char *ex = std::getenv("MGX_EMU_LANE_EXACT");
+    LP->exact = (ex && *ex == '1' && lane_exact_config(c, d, labeled_flags)) ? 1u : 0u;
     return true;
 }
 

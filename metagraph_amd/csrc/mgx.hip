@@ -299,6 +299,8 @@ struct AlignPlan {
     uint32_t cus = 0;                 // compute units of the device
     bool lane_ok = false;             // the lane-per-read kernel takes this batch's configuration (and got its scratch)
     uint32_t lane_blocks = 0;         // its resident wavefronts
+    uint64_t n_exact = 0;             // reads k_lane_exact finished before the sort (LP.exact): the last n_exact items of the sorted order
+    int key_bits = 0;                 // bits of the work-sort key (one more with LP.exact: LaneParams::done_key)
     LaneParams LP;
     uint64_t agg_cap = 1;             // alignments kept per query
     const ExtBuild *grp = nullptr;    // the 8-lane-group build the configuration extends on (group_build)
@@ -322,6 +324,13 @@ static int plan_lane(mgx_aligner *A, AlignPlan &pl) {
                  && lane_enabled(A->cfg, A->dcfg, A->graph->g.k, l.Lmax, A->no_fast, &LP, &lane_why,
                                  pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u)
                  && (A->opt.lane == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16);       // (a small batch: the spread / 64-lane kernels are quicker)
+    // The exact exit (lane_read.hpp lane_exact(), k_lane_exact): option exact = 1 forces it, 0 turns it off; automatic: on for the
+    // batches the lane kernel takes of its own accord — a small batch run with lane=1 keeps every read's fate in lane_read_dp()
+    // what the tests of its hand-over reasons pin.  (lane_enabled() filled the flag for the host model: decided here.)
+    LP.exact = (pl.lane_ok && A->opt.exact != 0 && lane_exact_config(A->cfg, A->dcfg, pl.labeled ? 1u : 0u)
+                && (A->opt.exact == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16)) ? 1u : 0u;
+    pl.key_bits = work_key_bits(pl.n) + (LP.exact ? 1 : 0);
+    LP.done_key = LP.exact ? 1u << work_key_bits(pl.n) : 0u;
     if (!pl.lane_ok) return MGX_OK;
     LP.max_cols = lane_max_cols(l.Lmax, A->dcfg.xdrop);
     LP.hash_slots = next_pow2(2ull * LP.max_cols);
@@ -410,7 +419,7 @@ static int size_buffers(mgx_aligner *A, AlignPlan &pl) {
     if (int rc = A->order.ensure(n * 4)) return rc;
     if (int rc = A->retry_list.ensure(n * 4 + 4)) return rc;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, pl.sort_tmp_bytes, A->work_key.as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
-                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, work_key_bits(n), A->hstream));
+                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, pl.key_bits, A->hstream));
     return A->sort_tmp.ensure(pl.sort_tmp_bytes);
 }
 
@@ -562,7 +571,7 @@ static int sort_by_work(mgx_aligner *A, AlignPlan &pl) {
     const uint64_t n = pl.n;
     k_iota<<<(uint32_t)((n + 255) / 256), 256, 0, A->hstream>>>(A->order_in.as<uint32_t>(), n);
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(A->sort_tmp.p, pl.sort_tmp_bytes, A->work_key.as<uint32_t>(), A->work_key_sorted.as<uint32_t>(),
-                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, work_key_bits(n), A->hstream));
+                                               A->order_in.as<uint32_t>(), A->order.as<uint32_t>(), (int)n, 0, pl.key_bits, A->hstream));
     HIP_TRY(clear_cursors(A, CUR_READ, CUR_READ));
     pl.P.order = A->order.as<uint32_t>();
     return MGX_OK;
@@ -586,27 +595,59 @@ static int choose_multi_pass(mgx_aligner *A, const AlignPlan &pl, bool *multi) {
     return MGX_OK;
 }
 
+// The lane kernel's device-side parameter block, list and counters: taken and cleared once per run of the stage, before the first
+// of k_lane_exact and k_lane.
+static int prepare_lane(mgx_aligner *A, AlignPlan &pl) {
+    LaneParams &LP = pl.LP;
+    if (int rc = A->lane_bail.ensure(pl.n * 4 + 4)) return rc;
+    if (int rc = A->lane_params.ensure(sizeof(LaneParams))) return rc;
+    if (int rc = A->lane_hist.ensure(64 * 8)) return rc;          // ([32 .. 41]: section timers of -DMGX_LANE_TIMERS builds, [LANE_HIST_EXACT])
+    HIP_TRY(hipMemsetAsync(A->lane_hist.p, 0, 64 * 8, A->hstream));
+    HIP_TRY(clear_cursors(A, CUR_LANE_BAIL, CUR_LANE_DONE));
+    LP.pk[0] = A->pk_fwd.as<uint64_t>(); LP.pk[1] = A->pk_rc.as<uint64_t>();
+    LP.iv[0] = A->iv_fwd.as<uint32_t>(); LP.iv[1] = A->iv_rc.as<uint32_t>();
+    LP.scratch = A->lane_scratch.as<uint8_t>();
+    LP.bail_list = A->lane_bail.as<uint32_t>();
+    LP.bail_count = cursor(A, CUR_LANE_BAIL);
+    LP.done_count = cursor(A, CUR_LANE_DONE);
+    LP.bail_hist = A->lane_hist.as<unsigned long long>();
+    return MGX_OK;
+}
+
+// The exact exit, between seeding and the work sort (plan_lane set LP.exact): k_lane_exact finishes every read whose first seed
+// spans the query and gives it the work key LP.done_key, which sorts it behind the reads that are still to be aligned; their number
+// comes back to the host, which launches k_lane on the items in front of them.
+static int exact_by_lanes(mgx_aligner *A, AlignPlan &pl) {
+    LaneParams &LP = pl.LP;
+    LP.P = pl.P;
+    LP.P.n_items = pl.n;
+    HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)pl.cus * 4 * 8 * 4, (pl.n + 63) / 64);
+    if (int rc = mgx_launch_lane_exact(A->lane_params.p, blocks, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit: %d", rc);
+    unsigned long long done = 0;
+    HIP_TRY(copy_sync(A, &done, cursor(A, CUR_LANE_DONE), 8, hipMemcpyDeviceToHost));      // (synchronises with the kernel)
+    pl.n_exact = done;
+    A->lane_exact = done;
+    return MGX_OK;
+}
+
 // Every read through the lane-per-read kernel first, in the sorted order; what it lists goes on to the extension kernel
 // (the plan's order and item count become that list; *all_done: it is empty).
 static int extend_by_lanes(mgx_aligner *A, AlignPlan &pl, bool *all_done) {
     AlignParams &P = pl.P;
     LaneParams &LP = pl.LP;
-    const uint64_t n = pl.n;
-    if (int rc = A->lane_bail.ensure(n * 4 + 4)) return rc;
-    if (int rc = A->lane_params.ensure(sizeof(LaneParams))) return rc;
-    if (int rc = A->lane_hist.ensure(64 * 8)) return rc;          // ([32 .. 63]: section timers of -DMGX_LANE_TIMERS builds)
-    HIP_TRY(hipMemsetAsync(A->lane_hist.p, 0, 64 * 8, A->hstream));
-    HIP_TRY(clear_cursors(A, CUR_LANE_BAIL, CUR_LANE_DONE));
+    // (the reads k_lane_exact finished are the last items of the sorted order: not k_lane's)
+    const uint64_t n = pl.n - pl.n_exact;
+    if (n == 0) {                 // every read left through the exact exit
+        A->lane_done = pl.n_exact;
+        A->kernels_ran |= MGX_KERNEL_LANE;
+        HIP_TRY(hipEventRecord(A->ev[EV_LANE_END], A->hstream));
+        *all_done = true;
+        return MGX_OK;
+    }
     LP.P = P;
     LP.P.n_items = n;
-    LP.pk[0] = A->pk_fwd.as<uint64_t>(); LP.pk[1] = A->pk_rc.as<uint64_t>();
-    LP.iv[0] = A->iv_fwd.as<uint32_t>(); LP.iv[1] = A->iv_rc.as<uint32_t>();
-    LP.scratch = A->lane_scratch.as<uint8_t>();
     LP.tag_seed = ++A->lane_epoch * 0x632BE5ABu;
-    LP.bail_list = A->lane_bail.as<uint32_t>();
-    LP.bail_count = cursor(A, CUR_LANE_BAIL);
-    LP.done_count = cursor(A, CUR_LANE_DONE);
-    LP.bail_hist = A->lane_hist.as<unsigned long long>();
     HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
     uint32_t blocks = (uint32_t)std::min<uint64_t>(pl.lane_blocks, (n + 63) / 64);
     if (int pct; env_int("MGX_LANE_BLOCKS_PCT", &pct)) blocks = std::max<uint32_t>(1u, (uint32_t)((uint64_t)blocks * (uint64_t)pct / 100));
@@ -757,13 +798,20 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     HIP_TRY(hipEventRecord(A->ev[EV_SEED_LANE_END], A->hstream));
     if (int rc = seed_by_waves(A, pl)) return rc;
     HIP_TRY(hipEventRecord(A->ev[EV_SEEDED], A->hstream));
-    if (int rc = sort_by_work(A, pl)) return rc;
-    HIP_TRY(hipEventRecord(A->ev[EV_SORTED], A->hstream));
-    bool multi = false;
-    if (int rc = choose_multi_pass(A, pl, &multi)) return rc;
     A->n_passes = 1;
     A->lane_done = 0;
+    A->lane_exact = 0;
     memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
+    // (with the exact exit the choice of the multi-pass extension comes before the sort: the exit belongs to the lane kernel's path)
+    bool multi = false;
+    const bool exact = pl.lane_ok && pl.LP.exact && n;
+    if (exact) { if (int rc = choose_multi_pass(A, pl, &multi)) return rc; }
+    const bool by_lanes = pl.lane_ok && !multi && n;
+    if (by_lanes) { if (int rc = prepare_lane(A, pl)) return rc; }
+    if (by_lanes && exact) { if (int rc = exact_by_lanes(A, pl)) return rc; }
+    if (int rc = sort_by_work(A, pl)) return rc;
+    HIP_TRY(hipEventRecord(A->ev[EV_SORTED], A->hstream));
+    if (!exact) { if (int rc = choose_multi_pass(A, pl, &multi)) return rc; }
     HIP_TRY(hipEventRecord(A->ev[EV_LANE_END], A->hstream));      // (recorded again behind the lane kernel, if it runs)
     bool all_done = false;        // every read finished in the lane kernel
     if (pl.lane_ok && !multi && n) {
@@ -793,6 +841,7 @@ int collect_stats(mgx_aligner *A, bool mapped, bool aligned) {
     s.n_fast_columns = ks.fast_columns;
     s.extend_kernels = A->kernels_ran;
     s.n_lane_reads = A->lane_done;
+    s.n_lane_exact_reads = A->lane_exact;
     s.n_lane_lines = ks.lane_lines; s.n_lane_columns = ks.lane_columns;
     for (int x = 0; x < 32; ++x) s.lane_bail_reads[x] = A->lane_hist_h[x];
     if (int on; aligned && A->seedlane_launched && env_int("MGX_SL_TIMERS", &on)) {
@@ -872,6 +921,10 @@ int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
         else if (key == "no_bt_runs") o.no_bt_runs = v;
         else if (key == "no_flat") o.no_flat = v;
         else if (key == "lane") o.lane = v;
+        else if (key == "exact") {
+            if (v < -1 || v > 1) return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
+            o.exact = v;
+        }
         else if (key == "device_share") o.device_share = std::max(1, std::min(v, 64));
         else if (key == "map_pipe") o.map_pipe = v;
         else if (key == "seed_wps") o.seed_wps = v;

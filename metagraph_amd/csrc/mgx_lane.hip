@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
         int rc = LR_DONE;
         LaneResult R;
         R.words = 0; R.have_aln = 0;
-        if (active) rc = lane_read(LP, read, (uint32_t)item, pass, scratch, chip, ctr, R);
+        if (active) rc = lane_read_dp(LP, read, (uint32_t)item, pass, scratch, chip, ctr, R);       // (the exact exit: k_lane_exact, below)
         if (active && rc == LR_AGAIN) pass = 1; else holding = false;
         const bool done = active && rc == LR_DONE, bail = active && rc == LR_BAIL;
         // output-stream words of the wavefront's finished reads: one atomic, a prefix sum over the lanes
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
         const uint64_t te0 = cycle_clock();
 #endif
         if (done) {
-            lane_emit(LP, read, scratch, chip, R, so);
+            lane_emit_t<false>(LP, read, scratch, chip, R, so);
             uint32_t *rec = lane_record(LP, scratch, lane);
             gst(rec + 29, gld(rec + 29) + 1u); gst(rec + 30, gld(rec + 30) + R.rr.n_extensions);
             gst(rec + 31, gld(rec + 31) + (uint32_t)(R.rr.status != ST_OK));
@@ -150,11 +150,61 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
     }
 }
 
+// The exact exit (lane_read.hpp, lane_exact()) for launches with LaneParams::exact, BEFORE the work sort: every read whose first
+// seed spans the query gets its result record and output stream here, in closed form, and the work key LaneParams::done_key, which
+// sorts it behind every read that still has to be aligned; the host then launches k_lane on the items in front of them.  A kernel
+// of its own because k_lane has no register to spare — the same test inside its loop, in front of the DP, made the allocator
+// spill 33 VGPRs in the column loop, a mark tested where k_lane fetches its items cost 25 more spilled SGPRs there — and because
+// this way k_lane is the code it was: it never meets these reads.  One lane per read, in read order.
+__global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict__ LPp) {
+    const LaneParams &LP = *LPp;
+    const int lane = (int)threadIdx.x;
+    const uint64_t n_reads = LP.P.n_reads;
+    LaneChip chip;
+    chip.lane = lane; chip.qw = nullptr; chip.qstride = 0; chip.cold = nullptr; chip.cstride = 0;     // (the closed form needs neither)
+    uint32_t n_done = 0, n_cap = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_reads; base += (uint64_t)gridDim.x * 64) {
+        const uint64_t read = base + (uint64_t)lane;
+        LaneResult R;
+        R.words = 0;
+        LV<bool> hv;
+        hv.v = read < n_reads && lane_exact(LP, read, R);
+        if (!wave_ballot(hv)) continue;
+        // output-stream words of the wavefront's reads: one atomic, a prefix sum over the lanes (as k_lane)
+        LV<int32_t> wv;
+        wv.v = hv.v ? (int32_t)R.words : 0;
+        const LV<int32_t> pre = wave_prefix_sum_excl(wv);
+        const int32_t total = wave_sum(wv);
+        LV<uint64_t> sv;
+        sv.v = 0;
+        if (lane == 0) sv.v = atomicAdd(LP.P.out_cursor, (unsigned long long)total);
+        const uint64_t so = wave_bcast(sv, 0) + (uint64_t)pre.v;
+        if (hv.v) {
+            lane_emit_t<true>(LP, read, nullptr, chip, R, so);
+            gst(LP.P.work_key + read, LP.done_key);
+            ++n_done; n_cap += (uint32_t)(R.rr.status != ST_OK);
+        }
+    }
+    LV<int32_t> v;
+    v.v = (int32_t)n_done; const int32_t nd = wave_sum(v);
+    v.v = (int32_t)n_cap; const int32_t nc = wave_sum(v);
+    if (lane == 0 && nd) {
+        atomicAdd(LP.done_count, (unsigned long long)nd);
+        atomicAdd(LP.bail_hist + LANE_HIST_EXACT, (unsigned long long)nd);
+        if (nc) atomicAdd(&LP.P.stats->capacity_errors, (unsigned long long)nc);
+    }
+}
+
 // blocks = resident wavefronts (wavefront b owns LaneParams::scratch + b * wave_stride)
 // d_params: the LaneParams of this launch in device memory
 extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream) {
     static_assert(sizeof(LaneParams) == MGX_LANE_PARAMS_BYTES, "LaneParams differs from what mgx.hip passes");
     k_lane<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
+    return (int)hipGetLastError();
+}
+// the exact exit, between seeding and the work sort (LaneParams::exact; done_count and bail_hist start at zero and are k_lane's too)
+extern "C" int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, void *stream) {
+    k_lane_exact<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     return (int)hipGetLastError();
 }
 extern "C" int mgx_lane_waves_per_simd(void) { return MGX_LANE_WAVES_PER_SIMD; }
