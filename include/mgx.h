@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6: mgx_stats::n_lane_exact_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
+#define MGX_ABI_VERSION 6      /* still 6: symbols added only: mgx_annotation_load_columns_device / mgx_column_file_decode_device / mgx_column_decode_kernel_launch_counts
+                                * (`.column.annodbg` files decoded by kernels); before that mgx_stats::n_lane_exact_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
                                 * header) and the option exact; before that, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
                                 * (the mgx_results layout of a batch, written by kernels); before that mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
                                 * batch, written by kernels); before that mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
@@ -775,6 +776,24 @@ const char *mgx_column_file_label(const mgx_column_file *f, uint32_t j);      /*
 const uint64_t *mgx_column_file_col_begin(const mgx_column_file *f);          /* num_labels + 1 entries */
 const uint64_t *mgx_column_file_rows(const mgx_column_file *f);               /* the arguments of mgx_annotation_create_sparse */
 int mgx_annotation_create_from_file(const mgx_column_file *f, int device, mgx_annotation **out);
+/* mgx_column_file_read + mgx_annotation_create_from_file with the columns decoded by kernels: same contract, the
+ * same annotation (mgx_annotation_get_rows answers alike), the same error codes and messages for the same files.  The host reads
+ * the files and walks their headers (num_rows, the label encoder, per column the representation code and the container headers);
+ * the payloads of all columns (sd_vector low / high, bit_vector_stat bits, rrr_vector<63> bt / btnr) go to the device as they
+ * stand in the files, in one copy, and are decoded there into the columns' set rows, which mgx_annotation_create_sparse takes
+ * with on_device = 1.  The number of kernel launches and device allocations does not depend on the number of columns, and no row
+ * index is copied to the host: n_labels counts, the error record and nothing else.  Whenever the header walk or a kernel's check
+ * finds fault with a file, the host reader is run on it and ITS code and message are returned (bit_vector_il: MGX_ERR_UNSUPPORTED).
+ * names_out (may be NULL) receives a mgx_column_file with num_rows, num_labels, the labels and col_begin: its rows live on the
+ * device only, so mgx_column_file_rows returns NULL on it and mgx_annotation_create_from_file refuses it (MGX_ERR_INVALID); free
+ * it with mgx_column_file_free. */
+int mgx_annotation_load_columns_device(const char *const *paths, uint32_t n_paths, int device, mgx_annotation **out, mgx_column_file **names_out);
+/* Test hook: the same kernels, then the rows copied back into a host-owned mgx_column_file — what mgx_column_file_read returns,
+ * entry for entry. */
+int mgx_column_file_decode_device(const char *const *paths, uint32_t n_paths, int device, mgx_column_file **out);
+/* Test hook: out4 = kernel launches, device allocations, bytes copied host-to-device, bytes copied device-to-host by the two calls
+ * above — since the library was loaded (the copies inside mgx_annotation_create_sparse are not counted). */
+void mgx_column_decode_kernel_launch_counts(uint64_t *out4);
 
 #ifdef __cplusplus
 }

@@ -55,12 +55,17 @@ def read_edgemask(path, state, n_edges):
     return out
 
 
-def read_column_files(paths):
-    """mgx_column_file_read (host only): (n_rows, label names, col_begin, rows) of one or several `.column.annodbg` files."""
+def read_column_files(paths, on_device=False, device=0):
+    """mgx_column_file_read (host only): (n_rows, label names, col_begin, rows) of one or several `.column.annodbg` files.
+    on_device: mgx_column_file_decode_device, the same content decoded by the kernels of mgx_annotation_load_columns_device and
+    copied back."""
     L = capi.lib()
     arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
     h = C.c_void_p()
-    _check(L.mgx_column_file_read(arr, len(paths), C.byref(h)))
+    if on_device:
+        _check(L.mgx_column_file_decode_device(arr, len(paths), device, C.byref(h)))
+    else:
+        _check(L.mgx_column_file_read(arr, len(paths), C.byref(h)))
     try:
         n = L.mgx_column_file_num_labels(h)
         names = [L.mgx_column_file_label(h, j).decode() for j in range(n)]
@@ -69,6 +74,14 @@ def read_column_files(paths):
         return int(L.mgx_column_file_num_rows(h)), names, cb, rows
     finally:
         L.mgx_column_file_free(h)
+
+
+def column_decode_kernel_launch_counts():
+    """mgx_column_decode_kernel_launch_counts: [kernel launches, device allocations, bytes host-to-device, bytes device-to-host]
+    of mgx_annotation_load_columns_device / mgx_column_file_decode_device since the library was loaded."""
+    out = (C.c_uint64 * 4)()
+    capi.lib().mgx_column_decode_kernel_launch_counts(out)
+    return [int(x) for x in out]
 
 
 class Graph:
@@ -154,10 +167,24 @@ class Annotation:
         return self
 
     @classmethod
-    def load(cls, paths, device=0):
-        """`.column.annodbg` files written by the reference (ColumnCompressed::load / merge_load); label names in .labels."""
+    def load(cls, paths, device=0, on_device=False):
+        """`.column.annodbg` files written by the reference (ColumnCompressed::load / merge_load); label names in .labels.
+        on_device: mgx_annotation_load_columns_device, the columns decoded by kernels (the same annotation)."""
         if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
             paths = [paths]
+        if on_device:
+            L = capi.lib()
+            arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+            self = cls.__new__(cls)
+            self.h, names = C.c_void_p(), C.c_void_p()
+            self._cols = []
+            _check(L.mgx_annotation_load_columns_device(arr, len(paths), device, C.byref(self.h), C.byref(names)))
+            try:
+                self.n_rows, self.n_labels = int(L.mgx_column_file_num_rows(names)), int(L.mgx_column_file_num_labels(names))
+                self.labels = [L.mgx_column_file_label(names, j).decode() for j in range(self.n_labels)]
+            finally:
+                L.mgx_column_file_free(names)
+            return self
         n_rows, names, cb, rows = read_column_files(paths)
         self = cls.from_sparse(n_rows, cb, rows, device=device)
         self.labels = names

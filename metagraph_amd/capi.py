@@ -254,6 +254,10 @@ def lib():
     L.mgx_column_file_rows.argtypes = [C.c_void_p]
     L.mgx_column_file_rows.restype = C.POINTER(C.c_uint64)
     L.mgx_annotation_create_from_file.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.mgx_annotation_load_columns_device.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mgx_column_file_decode_device.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.mgx_column_decode_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_column_decode_kernel_launch_counts.restype = None
     L.mgx_graph_create.argtypes = [C.POINTER(BossView), C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_graph_destroy.argtypes = [C.c_void_p]
     L.mgx_graph_k.argtypes = [C.c_void_p]

@@ -390,12 +390,8 @@ inline std::string read_short_string(Cursor &c) {   // load_string, serializatio
     return std::string((const char *)s, n);
 }
 
-inline ColumnFile parse_columns(const uint8_t *data, size_t n) {
-    Cursor c(data, n);
-    ColumnFile f;
-    f.n_rows = c.be("num_rows");                     // annotate_column_compressed.cpp:452
-    if (f.n_rows >= (1ull << 40)) throw ParseError("more rows than the device matrix addresses (2^40)");
-    // LabelEncoder<std::string>::load, annotation.cpp:46-86
+// LabelEncoder<std::string>::load, annotation.cpp:46-86: the labels in decode order.  data: the image c walks
+inline void read_label_encoder(Cursor &c, const uint8_t *data, std::vector<std::string> &labels) {
     if (c.left() >= 7 && !memcmp(data + c.at(), "LE-v2.0", 7)) {
         c.take(7, "label encoder");
         // VectorSet = tsl::ordered_set with IndexType uint64: protocol version, number of elements, bucket count, max load factor
@@ -405,7 +401,7 @@ inline ColumnFile parse_columns(const uint8_t *data, size_t n) {
         const uint64_t ne = c.le("label encoder"), nb = c.le("label encoder");
         c.take(4, "label encoder");
         if (ne > c.left() || nb > c.left()) throw ParseError("label encoder: counts exceed the file");
-        for (uint64_t i = 0; i < ne; ++i) { const uint64_t len = c.be("label"); const uint8_t *s = c.take(len, "label"); f.labels.emplace_back((const char *)s, len); }
+        for (uint64_t i = 0; i < ne; ++i) { const uint64_t len = c.be("label"); const uint8_t *s = c.take(len, "label"); labels.emplace_back((const char *)s, len); }
         c.take(nb * 16, "label encoder buckets");
     } else {
         // before v2.0: load_string_vector (the map's keys), load_number_vector (their codes), load_string_vector (decode order)
@@ -415,8 +411,16 @@ inline ColumnFile parse_columns(const uint8_t *data, size_t n) {
         read_int_vector(c, "label encoder", false);
         const uint64_t nd = c.be("label encoder");
         if (nd > c.left()) throw ParseError("label encoder: counts exceed the file");
-        for (uint64_t i = 0; i < nd; ++i) f.labels.push_back(read_short_string(c));
+        for (uint64_t i = 0; i < nd; ++i) labels.push_back(read_short_string(c));
     }
+}
+
+inline ColumnFile parse_columns(const uint8_t *data, size_t n) {
+    Cursor c(data, n);
+    ColumnFile f;
+    f.n_rows = c.be("num_rows");                     // annotate_column_compressed.cpp:452
+    if (f.n_rows >= (1ull << 40)) throw ParseError("more rows than the device matrix addresses (2^40)");
+    read_label_encoder(c, data, f.labels);
     for (size_t j = 0; j < f.labels.size(); ++j) {   // bit_vector_smart per label, :460-476
         const uint64_t code = c.be("column");
         uint64_t size = 0;

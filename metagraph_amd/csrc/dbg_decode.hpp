@@ -79,15 +79,16 @@ MGX_HD uint64_t dd_rrr_width(const uint64_t *bt, const uint8_t *wtab, uint64_t b
     return b < n_blocks ? wtab[dd_get(bt, b * 6, 6)] : 0;
 }
 
-// block b (63 bits): its number un-ranked as read_rrr63 does.  off[b]: the scanned widths.  C: DD_BINOM_ENTRIES binomials.
-MGX_HD uint64_t dd_rrr_block(const uint64_t *bt, const uint64_t *btnr, uint64_t btnr_bits, const uint64_t *off, const uint8_t *wtab,
-                             const uint64_t *C, uint64_t b, uint64_t *err, uint32_t check_early) {
+// block b (63 bits): its number, `len` bits at bit `pos` of btnr, un-ranked as read_rrr63 does.  C: DD_BINOM_ENTRIES binomials.
+// *status: 0, or 1 (block numbers end early) / 2 (block number outside its class) with a zero block.
+MGX_HD uint64_t dd_rrr_unrank(const uint64_t *bt, const uint64_t *btnr, uint64_t btnr_bits, uint64_t pos, const uint8_t *wtab,
+                              const uint64_t *C, uint64_t b, unsigned *status) {
+    *status = 0;
     const unsigned k = (unsigned)dd_get(bt, b * 6, 6);
     if (k == 63) return ~0ull >> 1;
     if (!k) return 0;
     const unsigned len = wtab[k];
-    const uint64_t pos = off[b];
-    if (pos > btnr_bits || len > btnr_bits - pos) { dd_fail(err, check_early, b); return 0; }
+    if (pos > btnr_bits || len > btnr_bits - pos) { *status = 1; return 0; }
     uint64_t nr = dd_get(btnr, pos, len);
     const bool inv = 2 * k > 63;
     unsigned j = inv ? 63 - k : k;                          // 1 .. 31
@@ -96,8 +97,16 @@ MGX_HD uint64_t dd_rrr_block(const uint64_t *bt, const uint64_t *btnr, uint64_t 
         const uint64_t c = C[(62 - p) * 32 + (j & 31)];
         if (j && nr >= c) { nr -= c; --j; block |= 1ull << p; }
     }
-    if (j || nr) { dd_fail(err, check_early + 1, b); return 0; }
+    if (j || nr) { *status = 2; return 0; }
     return inv ? ~block & (~0ull >> 1) : block;
+}
+// off[b]: the scanned widths
+MGX_HD uint64_t dd_rrr_block(const uint64_t *bt, const uint64_t *btnr, uint64_t btnr_bits, const uint64_t *off, const uint8_t *wtab,
+                             const uint64_t *C, uint64_t b, uint64_t *err, uint32_t check_early) {
+    unsigned status;
+    const uint64_t block = dd_rrr_unrank(bt, btnr, btnr_bits, off[b], wtab, C, b, &status);
+    if (status) dd_fail(err, check_early + status - 1, b);
+    return block;
 }
 
 // word wi of the decoded vector from the at most two blocks that overlap it; wi < dd_words(bits): the pad words come out zero

@@ -6,12 +6,8 @@
 #include <set>
 
 #include "../../include/mgx.h"
-#include "boss_files.hpp"
+#include "column_file.hpp"
 #include "kernel_units.hpp"
-
-struct mgx_column_file {
-    mgx::files::ColumnFile f;
-};
 
 namespace {
 int ffail(int code, const char *fmt, ...) {
@@ -118,10 +114,13 @@ uint64_t mgx_column_file_num_rows(const mgx_column_file *f) { return f ? f->f.n_
 uint32_t mgx_column_file_num_labels(const mgx_column_file *f) { return f ? (uint32_t)f->f.labels.size() : 0; }
 const char *mgx_column_file_label(const mgx_column_file *f, uint32_t j) { return f && j < f->f.labels.size() ? f->f.labels[j].c_str() : nullptr; }
 const uint64_t *mgx_column_file_col_begin(const mgx_column_file *f) { return f ? f->f.col_begin.data() : nullptr; }
-const uint64_t *mgx_column_file_rows(const mgx_column_file *f) { return f ? f->f.rows.data() : nullptr; }
+const uint64_t *mgx_column_file_rows(const mgx_column_file *f) { return f && !f->rows_on_device ? f->f.rows.data() : nullptr; }
 
 int mgx_annotation_create_from_file(const mgx_column_file *f, int device, mgx_annotation **out) {
     if (!f || !out) return ffail(MGX_ERR_INVALID, "mgx_annotation_create_from_file: bad arguments");
+    if (f->rows_on_device)
+        return ffail(MGX_ERR_INVALID, "mgx_annotation_create_from_file: this mgx_column_file is the names_out of mgx_annotation_load_columns_device: "
+                                      "it holds the labels and col_begin only, the rows went to the device and into that call's annotation");
     return mgx_annotation_create_sparse(f->f.n_rows, (uint32_t)f->f.labels.size(), f->f.col_begin.data(), f->f.rows.data(), 0, device, out);
 }
 

@@ -271,6 +271,14 @@ class HipAnnotation {
         if (int rc = mgx_annotation_create_sparse(n_rows, (uint32_t)(col_begin.size() - 1), col_begin.data(), rows.data(), 0, device, &a_))
             throw std::runtime_error(std::string("mgx_annotation_create_sparse: ") + mgx_last_error() + " (" + std::to_string(rc) + ")");
     }
+    // `.column.annodbg` files decoded by kernels (mgx_annotation_load_columns_device); label_names: the labels in column order
+    HipAnnotation(const std::vector<const char *> &paths, int device, uint64_t *n_rows, std::vector<std::string> *label_names) {
+        mgx_column_file *names = nullptr;
+        if (mgx_annotation_load_columns_device(paths.data(), (uint32_t)paths.size(), device, &a_, &names) != MGX_OK) throw std::runtime_error(mgx_last_error());
+        *n_rows = mgx_column_file_num_rows(names);
+        for (uint32_t j = 0, nl = mgx_column_file_num_labels(names); j < nl; ++j) label_names->emplace_back(mgx_column_file_label(names, j));
+        mgx_column_file_free(names);
+    }
     ~HipAnnotation() { mgx_annotation_destroy(a_); }
     HipAnnotation(const HipAnnotation &) = delete;
     uint32_t num_labels() const { return mgx_annotation_num_labels(a_); }

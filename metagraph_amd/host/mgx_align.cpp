@@ -41,7 +41,9 @@
 //                             --format-on-device)
 //             [--load-on-device]  GRAPH.dbg is decoded by kernels (mgx_graph_load_dbg_device): the host walks the file's headers, the
 //                             rrr blocks, the wavelet tree of W and `last` are decoded on the device.  The same graph, the same
-//                             output; the default decodes on the host (mgx_boss_file_read)
+//                             output; the default decodes on the host (mgx_boss_file_read).  With -a X.column.annodbg the
+//                             annotation's columns are decoded by kernels as well (mgx_annotation_load_columns_device) on the
+//                             device of the one annotation replica (-a goes with --devices 1); the same output
 //             [--devices D]   in-process multi-GPU: one graph replica per device, whole batches routed round-robin, no collective
 //             [--rccl-gather] with --devices D: one worker per device, batches in rounds of D; every round's device results are
 //                             gathered to device 0 over RCCL (mgx_gather_*: the C-ABI of north_star's "RCCL-over-xGMI only to
@@ -253,7 +255,13 @@ int main(int argc, char **argv) {
         std::unique_ptr<HipAnnotation> annotation;
         std::vector<std::string> label_names;
         if (!anno_paths.empty() && devices != 1) { fprintf(stderr, "error: -a with --devices 1 only (one annotation replica)\n"); return 1; }
-        if (!anno_paths.empty() && ends_with(anno_paths[0], ".annodbg")) {      // ColumnCompressed::merge_load
+        if (!anno_paths.empty() && ends_with(anno_paths[0], ".annodbg") && load_on_device) {      // ... with the columns decoded by kernels
+            uint64_t n_rows = 0;
+            try {
+                annotation = std::make_unique<HipAnnotation>(anno_paths, 0, &n_rows, &label_names);
+            } catch (const std::runtime_error &e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
+            if (n_rows != n) { fprintf(stderr, "error: the annotation has %llu rows, the graph %llu nodes\n", (unsigned long long)n_rows, (unsigned long long)n); return 1; }
+        } else if (!anno_paths.empty() && ends_with(anno_paths[0], ".annodbg")) {      // ColumnCompressed::merge_load
             mgx_column_file *cf = nullptr;
             if (mgx_column_file_read(anno_paths.data(), (uint32_t)anno_paths.size(), &cf) != MGX_OK) { fprintf(stderr, "error: %s\n", mgx_last_error()); return 1; }
             const uint32_t nl = mgx_column_file_num_labels(cf);
