@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 #define MGX_ABI_VERSION 6      /* still 6: symbols added only: mgx_annotation_load_columns_device / mgx_column_file_decode_device / mgx_column_decode_kernel_launch_counts
-                                * (`.column.annodbg` files decoded by kernels); before that mgx_stats::n_lane_exact_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
+                                * (`.column.annodbg` files decoded by kernels); before that mgx_stats::n_lane_exact_reads and (later) n_lane_exact_path_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
                                 * header) and the option exact; before that, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
                                 * (the mgx_results layout of a batch, written by kernels); before that mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
                                 * batch, written by kernels); before that mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
@@ -249,6 +249,9 @@ typedef struct mgx_stats {
     uint64_t n_lane_exact_reads; /* part of n_lane_reads: reads finished through the lane kernel's exact exit (k_lane_exact, csrc/lane_read.hpp
                                    lane_exact(): the first seed of the strand aligned first spans the query, so the result is the all-match
                                    alignment over the seed's nodes and no DP runs; n_lane_reads + sum(lane_bail_reads) == reads still holds) */
+    uint64_t n_lane_exact_path_reads; /* part of n_lane_reads, none of them in n_lane_exact_reads: reads finished through the exit's path
+                                   class (exact level 2): the first seed starts at the query's first character and ends at a fork or a
+                                   merge, every k-mer of the strand is a node; the same closed form over the strand's mapped nodes */
 } mgx_stats;
 enum { MGX_KERNEL_GRP8 = 1, MGX_KERNEL_GRP8_PRIM = 2, MGX_KERNEL_GRP8_ALT = 4, MGX_KERNEL_EXT64 = 8, MGX_KERNEL_LANE = 16,
        MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64 /* the label-aware builds of the 64-lane and the 8-lane kernel */ };
@@ -405,9 +408,11 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   groups_per_wave=n    8-lane kernel: n = 1 .. 8 groups of a wavefront take reads, 0 = all (default: from the batch size)
  *   multi_pass=0|1       one extension per read and launch (default: automatic from the seeds per read)
  *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic)
- *   exact=0|1            the lane kernel's exact exit: reads whose first seed spans the query are finished in closed form, without
- *                        DP (default: automatic — on for the batches the lane kernel takes of its own accord; 1: wherever the lane
- *                        kernel runs and the configuration allows it; never for label-aware batches)
+ *   exact=0|1|2          the lane kernel's exact exit: reads whose result is known when seeding ends are finished in closed form,
+ *                        without DP.  1: reads whose first seed spans the query; 2: also reads whose first seed starts at the query's
+ *                        first character and whose every k-mer is a node (perfect reads that cross a fork or a merge).  Default:
+ *                        automatic — level 2 for the batches the lane kernel takes of its own accord; 1 / 2: wherever the lane
+ *                        kernel runs and the configuration allows it; never for label-aware batches
  *   device_share=n       n handles are at work on this device at the same time (worker threads): this handle sizes its per-slot
  *                        arenas for 1 / n of the machine (default 1: all of it)
  *   seed_lane=0|1        the lane-per-read seeder in front of the seeding kernel (default: automatic)

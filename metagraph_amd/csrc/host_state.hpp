@@ -210,7 +210,8 @@ struct mgx_aligner {
     bool packed_valid = false;    // pk_* / iv_* hold this batch's strands (k <= 32 and the batch was mapped)
     uint32_t lane_epoch = 0;
     uint64_t lane_done = 0;
-    uint64_t lane_exact = 0;      // ... of them through the exact exit (k_lane_exact)
+    uint64_t lane_exact = 0;      // ... of them through the exact exit (k_lane_exact) with a first seed that spans the query
+    uint64_t lane_exact_path = 0; // ... and through its path class (level 2: every k-mer a node, the first seed shorter)
     unsigned long long lane_hist_h[32] = { 0 };
     DevBuf seedlane_scratch, seedlane_params, seedlane_bail, seedlane_hist;   // lane-per-read seeder: seed buffers, parameter block, the reads it leaves, why
     uint64_t seedlane_launched = 0;    // the last batch ran it (its counters are read back by collect_stats)
@@ -284,8 +285,9 @@ struct mgx_aligner {
         int multi_pass = -1;      // multi-pass extension on / off
         int no_compact = 0, no_alias = 0, no_bt_runs = 0, no_flat = 0;
         int lane = -1;            // the lane-per-read kernel in front of the extension kernel: -1 auto, 0 off, 1 forced
-        int exact = -1;           // the lane kernel's exact exit (k_lane_exact: reads whose first seed spans the query, no DP): -1 auto
-                                  // (batches the lane kernel takes of its own accord), 0 off, 1 on wherever the lane kernel runs
+        int exact = -1;           // the lane kernel's exact exit (k_lane_exact, no DP): -1 auto (level 2 for the batches the lane kernel
+                                  // takes of its own accord), 0 off, 1 / 2 that level wherever the lane kernel runs (1: reads whose
+                                  // first seed spans the query; 2: also reads whose every k-mer is a node, the path class)
         int seed_lane = -1;       // the lane-per-read seeder in front of the seeding kernel (seed_lane.hpp): -1 auto, 0 off, 1 forced
         int seed_wps = 8;         // wavefronts per SIMD of the short-read seeding kernel: 8 (64 VGPRs, spills) or 4 (102 VGPRs, tables in LDS)
         int device_share = 1;     // handles expected to run on this device at the same time (worker threads, -p N): the per-slot

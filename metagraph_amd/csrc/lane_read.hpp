@@ -1403,16 +1403,44 @@ MGX_DEV int lane_read_dp(const LaneParams &LP, uint64_t read, const uint32_t ite
 // right_end_bonus, and only this one reaches it.  The score must pass min_path_score and min_cell_score (backtrack's
 // min_start_score, aln_both's threshold): a read whose full score does not runs the DP as ever, as does every read that
 // lane_read_dp() would turn away before it looks at its first seed (length, header status, a second strand to align).
-// Returns whether R is filled (as lane_read_dp() fills it for LR_DONE; no extension ran: n_extensions = n_columns = 0).
-MGX_DEV bool lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R) {
+//
+// The path class (LaneParams::exact >= 2): the first seed starts at the query's first character (clipping 0, offset 0) but ends
+// short of the query — UniMEM seeds end where the graph forks or merges — and every k-mer of the strand is a node all the same.
+// Two consecutive k-mers that are both nodes are joined by an edge, so past the seed's end the strand's next node is a child of
+// the head column's node and the only one whose character scores a match: the all-match column stays the one top of the queue
+// to the query's end exactly as inside a seed, every side branch carries a mismatch or a gap and ends below the full score, and
+// the later seeds, whose last nodes lie on this path with the full prefix score, are found dead by check_seed.  Same score, same
+// CIGAR; the nodes are the strand's mapped nodes, which is where LANE_EMIT_EXACT takes them from anyway.
+enum { LANE_EXACT_NONE = 0, LANE_EXACT_SPAN = 1, LANE_EXACT_PATH = 2 };
+
+// whether none of the n node indices at p is 0 (a k-mer that is not in the graph), with the widest loads p's alignment allows:
+// single words up to the first 16-byte boundary, four nodes to a load from there on, single words for the rest
+struct alignas(16) LaneNodeQuad { uint32_t v[4]; };
+MGX_DEV bool lane_all_nodes(const uint32_t *p, const int32_t n) {
+    int32_t x = 0;
+    for (; x < n && ((uintptr_t)(p + x) & 15u); ++x)
+        if (!gld(p + x)) return false;
+    for (; x + 4 <= n; x += 4) {
+        const LaneNodeQuad q = gld((const LaneNodeQuad *)(p + x));
+        if (!q.v[0] || !q.v[1] || !q.v[2] || !q.v[3]) return false;
+    }
+    for (; x < n; ++x)
+        if (!gld(p + x)) return false;
+    return true;
+}
+
+// The predicate alone: LANE_EXACT_NONE, or the class the read is in; *strand: the strand aligned, hdr4: num_matching and seed
+// counts of both strands as the header has them (for the result record).  The cheap header tests come first; the node array is
+// read only for a read that passed them all and whose first seed ends short of the query.
+MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t *L_out, int *strand, uint32_t hdr4[4]) {
     const AlignParams &P = LP.P;
     const DevConfig &cfg = P.cfg;
-    if (P.labeled) return false;
+    if (P.labeled) return LANE_EXACT_NONE;
     const int32_t k = (int32_t)P.g.k;
     const int32_t L = (int32_t)(gld(P.offsets + read + 1) - gld(P.offsets + read));
-    if (L > (int32_t)P.lim.Lmax || L > LANE_MAX_L || L < k) return false;
+    if (L > (int32_t)P.lim.Lmax || L > LANE_MAX_L || L < k) return LANE_EXACT_NONE;
     const SeedHdr *hp = P.seed_hdr + read;
-    if (gld(&hp->status) != ST_OK) return false;
+    if (gld(&hp->status) != ST_OK) return LANE_EXACT_NONE;
     const uint32_t nm0 = gld(&hp->num_matching[0]), nm1 = gld(&hp->num_matching[1]);
     const int32_t ns0 = (int32_t)gld(&hp->n_seeds[0]), ns1 = (int32_t)gld(&hp->n_seeds[1]);
     const bool have_rc = cfg.fwd_and_rc != 0;
@@ -1422,29 +1450,54 @@ MGX_DEV bool lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R
     if (have_rc) {
         const uint32_t m_first = first ? nm1 : nm0, m_second = first ? nm0 : nm1;
         const int32_t n_second = first ? ns0 : ns1;
-        if ((double)m_second >= (double)m_first * cfg.rel_score_cutoff && n_second > 0) return false;
+        if ((double)m_second >= (double)m_first * cfg.rel_score_cutoff && n_second > 0) return LANE_EXACT_NONE;
     }
-    if ((s ? ns1 : ns0) <= 0) return false;
+    if ((s ? ns1 : ns0) <= 0) return LANE_EXACT_NONE;
     const DevSeed *s0 = P.seed_stream + gld(&hp->off) + (s ? ns0 : 0);
-    if (!(gld(&s0->clipping) == 0 && (int32_t)gld(&s0->length) == L && gld(&s0->offset) == 0)) return false;
+    if (!(gld(&s0->clipping) == 0 && gld(&s0->offset) == 0)) return LANE_EXACT_NONE;
+    const int32_t len = (int32_t)gld(&s0->length);
+    if (len != L && LP.exact < 2u) return LANE_EXACT_NONE;
     const int32_t full = LP.self_score * L + cfg.left_end_bonus + cfg.right_end_bonus;
-    if (full < cfg.min_path_score || full < cfg.min_cell_score) return false;
+    if (full < cfg.min_path_score || full < cfg.min_cell_score) return LANE_EXACT_NONE;
+    if (len != L) {
+        // the path class.  The k-mer behind the seed's last one first: where the seed ended at a character the graph does not
+        // have — most reads that come this far and are not in the class — that one word settles it
+        const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
+        const int32_t nk = L - k + 1, next = len - k + 1;
+        if (next > 0 && next < nk && !gld(rn + next)) return LANE_EXACT_NONE;
+        if (!lane_all_nodes(rn, nk)) return LANE_EXACT_NONE;
+    }
+    *L_out = L; *strand = s;
+    hdr4[0] = nm0; hdr4[1] = nm1; hdr4[2] = (uint32_t)ns0; hdr4[3] = (uint32_t)ns1;
+    return len == L ? LANE_EXACT_SPAN : LANE_EXACT_PATH;
+}
+
+// Returns the class if R is filled (as lane_read_dp() fills it for LR_DONE; no extension ran: n_extensions = n_columns = 0),
+// else LANE_EXACT_NONE.  The closed form is the same for both classes.
+MGX_DEV int lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R) {
+    int32_t L = 0;
+    int s = 0;
+    uint32_t h[4];
+    const int cls = lane_exact_class(LP, read, &L, &s, h);
+    if (cls == LANE_EXACT_NONE) return cls;
+    const int32_t k = (int32_t)LP.P.g.k;
     ReadResult &rr = R.rr;
     rr.status = ST_OK; rr.n_alignments = 0; rr.score = 0; rr.offset = 0; rr.n_nodes = rr.n_cigar = rr.seq_len = 0;
     rr.orientation = 0; rr.stream_off = 0;
-    rr.num_matches_fwd = nm0; rr.num_matches_rc = nm1; rr.n_seeds_fwd = (uint32_t)ns0; rr.n_seeds_rc = (uint32_t)ns1;
+    rr.num_matches_fwd = h[0]; rr.num_matches_rc = h[1]; rr.n_seeds_fwd = h[2]; rr.n_seeds_rc = h[3];
     rr.n_extensions = 0; rr.n_columns = 0;
     R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0; R.label = 0;
-    R.score = full; R.offset = 0; R.clip = 0; R.end_clip = 0; R.n_runs = 1; R.j_hi = 0; R.n_nodes = L - k + 1; R.n_seq = L;
+    R.score = LP.self_score * L + LP.P.cfg.left_end_bonus + LP.P.cfg.right_end_bonus;
+    R.offset = 0; R.clip = 0; R.end_clip = 0; R.n_runs = 1; R.j_hi = 0; R.n_nodes = L - k + 1; R.n_seq = L;
     R.words = (uint32_t)R.n_nodes + 1u + ((uint32_t)L + 3) / 4;
-    return true;
+    return cls;
 }
 
 // One read, as the host model calls it: the exact exit where it is on, else the DP.  (On the device the two are two kernels,
 // mgx_lane.hip: k_lane_exact runs lane_exact() on every read before the work sort, k_lane runs lane_read_dp() on the others.)
 MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, const int pass, uint8_t *scratch, const LaneChip &chip,
                       LaneCounters &ctr, LaneResult &R) {
-    if (!pass && LP.exact && lane_exact(LP, read, R)) return LR_DONE;
+    if (!pass && LP.exact && lane_exact(LP, read, R) != LANE_EXACT_NONE) return LR_DONE;
     return lane_read_dp(LP, read, item, pass, scratch, chip, ctr, R);
 }
 

@@ -57,14 +57,18 @@ struct LaneParams {
     unsigned long long *done_count;
     unsigned long long *bail_hist;       // [32] reads passed on, by the LANE_BAIL code of the test that sent them (lane_read.hpp);
                                          // [LANE_HIST_EXACT] reads finished through the exact exit (part of *done_count, which is
-                                         // what the host reads; the word is there for probes of a launch's counters)
+                                         // what the host reads; the word is there for probes of a launch's counters);
+                                         // [LANE_HIST_EXACT_PATH] those of them without a spanning first seed (the path class)
     // (behind what k_lane reads, whose offsets stay what they were)
-    uint32_t exact;                      // 1: a read whose first seed spans the query is finished without DP (lane_read.hpp, the exact
-                                         // exit; only where lane_exact_config() holds).  0 by default: every read runs its columns
+    uint32_t exact;                      // the level of the exact exit (lane_read.hpp; only where lane_exact_config() holds).  1: a read whose
+                                         // first seed spans the query is finished without DP; 2: also a read whose first seed starts at
+                                         // the query's first character and whose every k-mer is a node (the path class).  0 by default:
+                                         // every read runs its columns
     uint32_t done_key;                   // exact, on the device: the work key k_lane_exact gives the reads it finished — above every
                                          // key of the seeding phase, so that the work sort puts them behind the items k_lane is launched on
 };
 constexpr int LANE_HIST_EXACT = 48;        // (bail_hist has 64 words; [32 .. 41] are the section timers of -DMGX_LANE_TIMERS builds)
+constexpr int LANE_HIST_EXACT_PATH = 49;
 
 // columns of an extension along one path: the root, one per query character, the deletions past the query's end that the x-drop
 // still allows, the spare slot of the `size >= capacity - 1` test (a read that needs more goes to the group kernel)
@@ -91,7 +95,9 @@ inline uint64_t lane_wave_scratch_bytes(uint32_t max_cols, uint64_t rest_stride)
 // Whether the exact exit (lane_read.hpp lane_exact(), mgx_lane.hip k_lane_exact) may be on, given that lane_enabled() holds: the conditions, beyond lane_enabled()'s, under
 // which a read whose first seed spans the query has the all-match alignment over the seed's nodes as its one result, with the score
 // m L + left_end_bonus + right_end_bonus (DESIGN.md 3.4 "the exact exit").  What depends on the read's length — min_path_score
-// and min_cell_score against that score — is tested per read in lane_exact().
+// and min_cell_score against that score — is tested per read in lane_exact().  The path class of level 2 (first seed at the query's
+// first character, every k-mer of the strand a node) stands on the same conditions: past the seed's end the strand's next node is
+// the one child that scores a match, so the first two items carry the fork argument from "inside the seed" to "along the path".
 //  - every mismatch scores strictly below a match and a gap strictly below 0: no second alignment reaches the full score, and at a
 //    fork the all-match child is the only top of the extender's queue (no tie for the order of equal columns to resolve);
 //  - right_end_bonus >= 0: an alignment that stops short of the query's end cannot score above the full one;
@@ -143,10 +149,11 @@ inline bool lane_enabled(const mgx_config &c, const DevConfig &d, uint32_t k, ui
     if (c.left_end_bonus < 0) return no("negative left end bonus");
     if (!(c.rel_score_cutoff >= 0.0 && c.rel_score_cutoff <= 1.0)) return no("rel_score_cutoff outside [0, 1]");
     LP->self_score = m;
-    // (the host model: MGX_EMU_LANE_EXACT=1 sets the exact exit where the configuration allows it; the product's plan_lane()
-    // decides by its own rule and overwrites this)
+    // (the host model: MGX_EMU_LANE_EXACT=1 / 2 sets the exact exit's level where the configuration allows it; the product's
+    // plan_lane() decides by its own rule and overwrites this)
     const char *ex = std::getenv("MGX_EMU_LANE_EXACT");
-    LP->exact = (ex && *ex == '1' && lane_exact_config(c, d, labeled_flags)) ? 1u : 0u;
+    const uint32_t level = (ex && (*ex == '1' || *ex == '2') && !ex[1]) ? (uint32_t)(*ex - '0') : 0u;
+    LP->exact = (level && lane_exact_config(c, d, labeled_flags)) ? level : 0u;
     return true;
 }
 

@@ -324,11 +324,12 @@ static int plan_lane(mgx_aligner *A, AlignPlan &pl) {
                  && lane_enabled(A->cfg, A->dcfg, A->graph->g.k, l.Lmax, A->no_fast, &LP, &lane_why,
                                  pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u)
                  && (A->opt.lane == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16);       // (a small batch: the spread / 64-lane kernels are quicker)
-    // The exact exit (lane_read.hpp lane_exact(), k_lane_exact): option exact = 1 forces it, 0 turns it off; automatic: on for the
+    // The exact exit (lane_read.hpp lane_exact(), k_lane_exact): option exact = 1 / 2 forces it at that level (1: reads whose first
+    // seed spans the query; 2: also the path class), 0 turns it off; automatic: level 2 for the
     // batches the lane kernel takes of its own accord — a small batch run with lane=1 keeps every read's fate in lane_read_dp()
     // what the tests of its hand-over reasons pin.  (lane_enabled() filled the flag for the host model: decided here.)
     LP.exact = (pl.lane_ok && A->opt.exact != 0 && lane_exact_config(A->cfg, A->dcfg, pl.labeled ? 1u : 0u)
-                && (A->opt.exact == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16)) ? 1u : 0u;
+                && (A->opt.exact >= 1 || pl.n >= (uint64_t)pl.lane_blocks * 16)) ? (A->opt.exact >= 1 ? (uint32_t)A->opt.exact : 2u) : 0u;
     pl.key_bits = work_key_bits(pl.n) + (LP.exact ? 1 : 0);
     LP.done_key = LP.exact ? 1u << work_key_bits(pl.n) : 0u;
     if (!pl.lane_ok) return MGX_OK;
@@ -615,7 +616,7 @@ static int prepare_lane(mgx_aligner *A, AlignPlan &pl) {
 }
 
 // The exact exit, between seeding and the work sort (plan_lane set LP.exact): k_lane_exact finishes every read whose first seed
-// spans the query and gives it the work key LP.done_key, which sorts it behind the reads that are still to be aligned; their number
+// spans the query (at level 2 also every read of the path class, lane_read.hpp) and gives it the work key LP.done_key, which sorts it behind the reads that are still to be aligned; their number
 // comes back to the host, which launches k_lane on the items in front of them.
 static int exact_by_lanes(mgx_aligner *A, AlignPlan &pl) {
     LaneParams &LP = pl.LP;
@@ -627,7 +628,11 @@ static int exact_by_lanes(mgx_aligner *A, AlignPlan &pl) {
     unsigned long long done = 0;
     HIP_TRY(copy_sync(A, &done, cursor(A, CUR_LANE_DONE), 8, hipMemcpyDeviceToHost));      // (synchronises with the kernel)
     pl.n_exact = done;
-    A->lane_exact = done;
+    unsigned long long path = 0;      // ... of them in the path class (level 2): counted apart, the first-seed-spans class keeps its counter
+    if (LP.exact >= 2u && done)
+        HIP_TRY(copy_sync(A, &path, A->lane_hist.as<unsigned long long>() + LANE_HIST_EXACT_PATH, 8, hipMemcpyDeviceToHost));
+    A->lane_exact = done - path;
+    A->lane_exact_path = path;
     return MGX_OK;
 }
 
@@ -801,6 +806,7 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     A->n_passes = 1;
     A->lane_done = 0;
     A->lane_exact = 0;
+    A->lane_exact_path = 0;
     memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
     // (with the exact exit the choice of the multi-pass extension comes before the sort: the exit belongs to the lane kernel's path)
     bool multi = false;
@@ -842,6 +848,7 @@ int collect_stats(mgx_aligner *A, bool mapped, bool aligned) {
     s.extend_kernels = A->kernels_ran;
     s.n_lane_reads = A->lane_done;
     s.n_lane_exact_reads = A->lane_exact;
+    s.n_lane_exact_path_reads = A->lane_exact_path;
     s.n_lane_lines = ks.lane_lines; s.n_lane_columns = ks.lane_columns;
     for (int x = 0; x < 32; ++x) s.lane_bail_reads[x] = A->lane_hist_h[x];
     if (int on; aligned && A->seedlane_launched && env_int("MGX_SL_TIMERS", &on)) {
@@ -922,7 +929,7 @@ int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
         else if (key == "no_flat") o.no_flat = v;
         else if (key == "lane") o.lane = v;
         else if (key == "exact") {
-            if (v < -1 || v > 1) return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
+            if (v < -1 || v > 2) return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
             o.exact = v;
         }
         else if (key == "device_share") o.device_share = std::max(1, std::min(v, 64));

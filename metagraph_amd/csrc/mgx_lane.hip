@@ -151,7 +151,8 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
 }
 
 // The exact exit (lane_read.hpp, lane_exact()) for launches with LaneParams::exact, BEFORE the work sort: every read whose first
-// seed spans the query gets its result record and output stream here, in closed form, and the work key LaneParams::done_key, which
+// seed spans the query (and, at level 2, every read of the path class: first seed at the query's first character, every k-mer a node;
+// counted apart in bail_hist[LANE_HIST_EXACT_PATH]) gets its result record and output stream here, in closed form, and the work key LaneParams::done_key, which
 // sorts it behind every read that still has to be aligned; the host then launches k_lane on the items in front of them.  A kernel
 // of its own because k_lane has no register to spare — the same test inside its loop, in front of the DP, made the allocator
 // spill 33 VGPRs in the column loop, a mark tested where k_lane fetches its items cost 25 more spilled SGPRs there — and because
@@ -162,13 +163,14 @@ __global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict_
     const uint64_t n_reads = LP.P.n_reads;
     LaneChip chip;
     chip.lane = lane; chip.qw = nullptr; chip.qstride = 0; chip.cold = nullptr; chip.cstride = 0;     // (the closed form needs neither)
-    uint32_t n_done = 0, n_cap = 0;
+    uint32_t n_done = 0, n_path = 0, n_cap = 0;
     for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_reads; base += (uint64_t)gridDim.x * 64) {
         const uint64_t read = base + (uint64_t)lane;
         LaneResult R;
         R.words = 0;
         LV<bool> hv;
-        hv.v = read < n_reads && lane_exact(LP, read, R);
+        const int cls = read < n_reads ? lane_exact(LP, read, R) : LANE_EXACT_NONE;
+        hv.v = cls != LANE_EXACT_NONE;
         if (!wave_ballot(hv)) continue;
         // output-stream words of the wavefront's reads: one atomic, a prefix sum over the lanes (as k_lane)
         LV<int32_t> wv;
@@ -182,15 +184,17 @@ __global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict_
         if (hv.v) {
             lane_emit_t<true>(LP, read, nullptr, chip, R, so);
             gst(LP.P.work_key + read, LP.done_key);
-            ++n_done; n_cap += (uint32_t)(R.rr.status != ST_OK);
+            ++n_done; n_path += (uint32_t)(cls == LANE_EXACT_PATH); n_cap += (uint32_t)(R.rr.status != ST_OK);
         }
     }
     LV<int32_t> v;
     v.v = (int32_t)n_done; const int32_t nd = wave_sum(v);
     v.v = (int32_t)n_cap; const int32_t nc = wave_sum(v);
+    v.v = (int32_t)n_path; const int32_t np = wave_sum(v);
     if (lane == 0 && nd) {
         atomicAdd(LP.done_count, (unsigned long long)nd);
         atomicAdd(LP.bail_hist + LANE_HIST_EXACT, (unsigned long long)nd);
+        if (np) atomicAdd(LP.bail_hist + LANE_HIST_EXACT_PATH, (unsigned long long)np);
         if (nc) atomicAdd(&LP.P.stats->capacity_errors, (unsigned long long)nc);
     }
 }
