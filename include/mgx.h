@@ -251,7 +251,8 @@ typedef struct mgx_stats {
                                    alignment over the seed's nodes and no DP runs; n_lane_reads + sum(lane_bail_reads) == reads still holds) */
     uint64_t n_lane_exact_path_reads; /* part of n_lane_reads, none of them in n_lane_exact_reads: reads finished through the exit's path
                                    class (exact level 2): the first seed starts at the query's first character and ends at a fork or a
-                                   merge, every k-mer of the strand is a node; the same closed form over the strand's mapped nodes */
+                                   merge, every k-mer of the strand is a node; the same closed form over the strand's mapped nodes.
+                                   Both counters count label-aware reads too (k_lane_exact_labeled: one label all along) */
 } mgx_stats;
 enum { MGX_KERNEL_GRP8 = 1, MGX_KERNEL_GRP8_PRIM = 2, MGX_KERNEL_GRP8_ALT = 4, MGX_KERNEL_EXT64 = 8, MGX_KERNEL_LANE = 16,
        MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64 /* the label-aware builds of the 64-lane and the 8-lane kernel */ };
@@ -412,7 +413,11 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *                        without DP.  1: reads whose first seed spans the query; 2: also reads whose first seed starts at the query's
  *                        first character and whose every k-mer is a node (perfect reads that cross a fork or a merge).  Default:
  *                        automatic — level 2 for the batches the lane kernel takes of its own accord; 1 / 2: wherever the lane
- *                        kernel runs and the configuration allows it; never for label-aware batches
+ *                        kernel runs and the configuration allows it.  Label-aware batches (wherever the lane kernel takes them:
+ *                        no dummy node's row holds a label) are included, at either level and in the automatic default: there
+ *                        the exit takes the reads that keep one label all along — the label filter leaves the seeds one label L
+ *                        and every node of the path has the row { L } — and the label list of the alignment is [L]; with one
+ *                        seed per k-mer the first class is the reads of k characters.  Results never depend on the option
  *   device_share=n       n handles are at work on this device at the same time (worker threads): this handle sizes its per-slot
  *                        arenas for 1 / n of the machine (default 1: all of it)
  *   seed_lane=0|1        the lane-per-read seeder in front of the seeding kernel (default: automatic)

@@ -1429,21 +1429,127 @@ MGX_DEV bool lane_all_nodes(const uint32_t *p, const int32_t n) {
     return true;
 }
 
+// ---- label-aware batches (LabeledAligner; DESIGN.md 3.4 "one label all along") ----
+// The one-label seed filter of lane_read_dp() (its block under `if (P.labeled)` at pass 0; LabeledAligner::filter_seeds,
+// aligner_labeled.cpp:612-721, in the one-label case) as a function of the exit's own: k_lane has no register to spare, so its copy
+// stays where it is, statement for statement, and tests/test_lane_exact_labels.py pins the two equal (seed counts and matches of
+// every class read against the DP's record).  Both strands: every seed's first node has a one-label row, the same label for all
+// (else false: lane_read_dp() would hand the read over); a strand whose covered positions fall below min_exact_match * L loses
+// its seeds; num_matching is recounted over the seeds left.  ns / nm: the header's values in, the filtered ones out.
+MGX_DEV bool lane_exact_label_filter(const AlignParams &P, const uint64_t read, const SeedHdr *hp, const int32_t L, const bool have_rc,
+                                     int32_t ns[2], uint32_t nm[2], uint32_t *label_out) {
+    const int32_t k = (int32_t)P.g.k;
+    uint32_t label = 0;
+    bool have_label = false;
+    const int32_t ns0_h = ns[0];                                  // (strand 1's seeds follow strand 0's in the stream)
+    for (int s2 = 0; s2 < 2; ++s2) {
+        const int32_t n_in = ns[s2];
+        if (!n_in) continue;
+        if (s2 && !have_rc) continue;
+        const DevSeed *sd0 = P.seed_stream + gld(&hp->off) + (s2 ? ns0_h : 0);
+        const uint32_t *rn = (s2 ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
+        uint64_t cov[4] = { 0, 0, 0, 0 };
+        uint32_t cnt_m = 0;
+        int32_t last_end = 0;
+        bool counting = true;
+        for (int32_t j = 0; j < n_in; ++j) {
+            const DevSeed *sj = sd0 + j;
+            const int32_t cl = (int32_t)gld(&sj->clipping), so = (int32_t)gld(&sj->offset), len = (int32_t)gld(&sj->length);
+            const uint32_t node0 = so == 0 ? gld(rn + cl) : gld(&sj->node);
+            uint64_t h = 0;
+            if (node0 && node0 <= P.g.n && (uint64_t)node0 - 1 < P.anno_rows) h = gld(P.anno_head + ((uint64_t)node0 - 1));
+            if ((h & 0xFFFF) != 1) return false;
+            const uint32_t lbl = (uint32_t)(h >> 16);
+            if (!have_label) { label = lbl; have_label = true; } else if (lbl != label) return false;
+            const int32_t lo = cl, hi = imin(cl + k - so, L);
+#pragma unroll
+            for (int wq = 0; wq < 4; ++wq) {                       // bits [lo, hi) of the 256-position indicator
+                const int32_t a = imin(imax(lo - 64 * wq, 0), 64), b = imin(imax(hi - 64 * wq, 0), 64);
+                const uint64_t below_b = b >= 64 ? ~0ull : (1ull << b) - 1ull, below_a = a >= 64 ? ~0ull : (1ull << a) - 1ull;
+                cov[wq] |= below_b & ~below_a;
+            }
+            if (counting) {
+                const int32_t q_end = cl + len;
+                if (q_end > last_end) cnt_m += (uint32_t)((q_end - cl) - (cl < last_end ? last_end - cl : 0));
+                last_end = q_end;
+                if (so) counting = false;
+            }
+        }
+        const uint32_t cnt = (uint32_t)(popc64(cov[0]) + popc64(cov[1]) + popc64(cov[2]) + popc64(cov[3]));
+        const bool keep = !((double)cnt < P.cfg.min_exact_match * (double)L);
+        ns[s2] = keep ? n_in : 0; nm[s2] = keep ? cnt_m : 0u;
+    }
+    *label_out = label;
+    return have_label;
+}
+
+// whether each of the n nodes at p is a node of the graph whose row is exactly { label } — head word: one label, this one — in one
+// pass (a k-mer that is not in the graph fails with the rest).  Four nodes to a 16-byte load as lane_all_nodes(), then their four
+// rows requested before the first is looked at: the gathers are independent, a round trip each, and one at a time a lane would
+// wait ~120 of them out in a row.  Leaves at the first group that fails.
+MGX_DEV bool lane_all_rows(const AlignParams &P, const uint32_t *p, const int32_t n, const uint32_t label) {
+    const uint64_t want = ((uint64_t)label << 16) | 1u, gn = P.g.n, rows = P.anno_rows;
+    const uint64_t *head = P.anno_head;
+    auto row_ok = [&](const uint32_t node) -> bool { return node && node <= gn && (uint64_t)node - 1 < rows; };
+    int32_t x = 0;
+    for (; x < n && ((uintptr_t)(p + x) & 15u); ++x) {
+        const uint32_t v = gld(p + x);
+        if (!row_ok(v) || gld(head + ((uint64_t)v - 1)) != want) return false;
+    }
+    for (; x + 4 <= n; x += 4) {
+        const LaneNodeQuad q = gld((const LaneNodeQuad *)(p + x));
+        if (!row_ok(q.v[0]) || !row_ok(q.v[1]) || !row_ok(q.v[2]) || !row_ok(q.v[3])) return false;
+        const uint64_t h0 = gld(head + ((uint64_t)q.v[0] - 1)), h1 = gld(head + ((uint64_t)q.v[1] - 1));
+        const uint64_t h2 = gld(head + ((uint64_t)q.v[2] - 1)), h3 = gld(head + ((uint64_t)q.v[3] - 1));
+        if (((h0 ^ want) | (h1 ^ want) | (h2 ^ want) | (h3 ^ want)) != 0) return false;
+    }
+    for (; x < n; ++x) {
+        const uint32_t v = gld(p + x);
+        if (!row_ok(v) || gld(head + ((uint64_t)v - 1)) != want) return false;
+    }
+    return true;
+}
+
 // The predicate alone: LANE_EXACT_NONE, or the class the read is in; *strand: the strand aligned, hdr4: num_matching and seed
-// counts of both strands as the header has them (for the result record).  The cheap header tests come first; the node array is
-// read only for a read that passed them all and whose first seed ends short of the query.
-MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t *L_out, int *strand, uint32_t hdr4[4]) {
+// counts of both strands for the result record — as the header has them, or, label-aware, as the label filter left them;
+// *label: the read's one label (label-aware), else 0.  The cheap header tests come first; the node array is read only for a read
+// that passed them all and whose first seed ends short of the query, and the rows along the path (label-aware) last of all.
+// LABELED: whether the batch may be label-aware (k_lane_exact, the kernel of the unlabeled batches, is compiled without that half:
+// its code is what it was); a label-aware batch under LABELED = false is refused.
+template <bool LABELED>
+MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t *L_out, int *strand, uint32_t hdr4[4], uint32_t *label_out) {
     const AlignParams &P = LP.P;
     const DevConfig &cfg = P.cfg;
-    if (P.labeled) return LANE_EXACT_NONE;
+    // (label-aware: only where no dummy node's row holds a label — the condition under which the lane reads rows at all; nothing
+    // of the annotation is touched before this)
+    if (P.labeled && (!LABELED || !(P.labeled & 2u))) return LANE_EXACT_NONE;
+    const bool labeled = LABELED && P.labeled != 0;
     const int32_t k = (int32_t)P.g.k;
     const int32_t L = (int32_t)(gld(P.offsets + read + 1) - gld(P.offsets + read));
     if (L > (int32_t)P.lim.Lmax || L > LANE_MAX_L || L < k) return LANE_EXACT_NONE;
     const SeedHdr *hp = P.seed_hdr + read;
     if (gld(&hp->status) != ST_OK) return LANE_EXACT_NONE;
-    const uint32_t nm0 = gld(&hp->num_matching[0]), nm1 = gld(&hp->num_matching[1]);
-    const int32_t ns0 = (int32_t)gld(&hp->n_seeds[0]), ns1 = (int32_t)gld(&hp->n_seeds[1]);
+    uint32_t nm[2] = { gld(&hp->num_matching[0]), gld(&hp->num_matching[1]) };
+    int32_t ns[2] = { (int32_t)gld(&hp->n_seeds[0]), (int32_t)gld(&hp->n_seeds[1]) };
+    const int32_t ns0_h = ns[0];
     const bool have_rc = cfg.fwd_and_rc != 0;
+    const int32_t full = LP.self_score * L + cfg.left_end_bonus + cfg.right_end_bonus;
+    uint32_t label = 0;
+    if (labeled) {
+        // what needs no row first: the score thresholds, and a first seed at the query's first character (spanning it at level 1)
+        // on one strand at least — the filter removes seeds by the strand, so the first seed of the strand chosen below is one of these
+        if (full < cfg.min_path_score || full < cfg.min_cell_score) return LANE_EXACT_NONE;
+        bool cand = false;
+        for (int s2 = 0; s2 < (have_rc ? 2 : 1); ++s2) {
+            if (ns[s2] <= 0) continue;
+            const DevSeed *sf = P.seed_stream + gld(&hp->off) + (s2 ? ns0_h : 0);
+            cand = cand || (gld(&sf->clipping) == 0 && gld(&sf->offset) == 0 && ((int32_t)gld(&sf->length) == L || LP.exact >= 2u));
+        }
+        if (!cand) return LANE_EXACT_NONE;
+        if (!lane_exact_label_filter(P, read, hp, L, have_rc, ns, nm, &label)) return LANE_EXACT_NONE;
+    }
+    const uint32_t nm0 = nm[0], nm1 = nm[1];
+    const int32_t ns0 = ns[0], ns1 = ns[1];
     // align_both_directions (:738-755), as lane_read_dp(): the strand with more matches; a second strand to align is not for here
     const int first = nm0 >= nm1 ? 0 : 1;
     const int s = have_rc ? first : 0;
@@ -1453,32 +1559,36 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
         if ((double)m_second >= (double)m_first * cfg.rel_score_cutoff && n_second > 0) return LANE_EXACT_NONE;
     }
     if ((s ? ns1 : ns0) <= 0) return LANE_EXACT_NONE;
-    const DevSeed *s0 = P.seed_stream + gld(&hp->off) + (s ? ns0 : 0);
+    const DevSeed *s0 = P.seed_stream + gld(&hp->off) + (s ? ns0_h : 0);
     if (!(gld(&s0->clipping) == 0 && gld(&s0->offset) == 0)) return LANE_EXACT_NONE;
     const int32_t len = (int32_t)gld(&s0->length);
     if (len != L && LP.exact < 2u) return LANE_EXACT_NONE;
-    const int32_t full = LP.self_score * L + cfg.left_end_bonus + cfg.right_end_bonus;
     if (full < cfg.min_path_score || full < cfg.min_cell_score) return LANE_EXACT_NONE;
+    const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
+    const int32_t nk = L - k + 1;
     if (len != L) {
         // the path class.  The k-mer behind the seed's last one first: where the seed ended at a character the graph does not
         // have — most reads that come this far and are not in the class — that one word settles it
-        const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
-        const int32_t nk = L - k + 1, next = len - k + 1;
+        const int32_t next = len - k + 1;
         if (next > 0 && next < nk && !gld(rn + next)) return LANE_EXACT_NONE;
-        if (!lane_all_nodes(rn, nk)) return LANE_EXACT_NONE;
+        if (!labeled && !lane_all_nodes(rn, nk)) return LANE_EXACT_NONE;
     }
-    *L_out = L; *strand = s;
+    // label-aware: every node of the path has the row { label } — in the span class too: the filter saw each seed's first node
+    // only — and, in the path class, is a node at all: one pass over the node array
+    if (labeled && !lane_all_rows(P, rn, nk, label)) return LANE_EXACT_NONE;
+    *L_out = L; *strand = s; *label_out = label;
     hdr4[0] = nm0; hdr4[1] = nm1; hdr4[2] = (uint32_t)ns0; hdr4[3] = (uint32_t)ns1;
     return len == L ? LANE_EXACT_SPAN : LANE_EXACT_PATH;
 }
 
 // Returns the class if R is filled (as lane_read_dp() fills it for LR_DONE; no extension ran: n_extensions = n_columns = 0),
-// else LANE_EXACT_NONE.  The closed form is the same for both classes.
-MGX_DEV int lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R) {
+// else LANE_EXACT_NONE.  The closed form is the same for both classes; label-aware it carries the read's one label behind it.
+template <bool LABELED>
+MGX_DEV int lane_exact_t(const LaneParams &LP, const uint64_t read, LaneResult &R) {
     int32_t L = 0;
     int s = 0;
-    uint32_t h[4];
-    const int cls = lane_exact_class(LP, read, &L, &s, h);
+    uint32_t h[4], label = 0;
+    const int cls = lane_exact_class<LABELED>(LP, read, &L, &s, h, &label);
     if (cls == LANE_EXACT_NONE) return cls;
     const int32_t k = (int32_t)LP.P.g.k;
     ReadResult &rr = R.rr;
@@ -1486,11 +1596,14 @@ MGX_DEV int lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R)
     rr.orientation = 0; rr.stream_off = 0;
     rr.num_matches_fwd = h[0]; rr.num_matches_rc = h[1]; rr.n_seeds_fwd = h[2]; rr.n_seeds_rc = h[3];
     rr.n_extensions = 0; rr.n_columns = 0;
-    R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0; R.label = 0;
+    R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0; R.label = label;
     R.score = LP.self_score * L + LP.P.cfg.left_end_bonus + LP.P.cfg.right_end_bonus;
     R.offset = 0; R.clip = 0; R.end_clip = 0; R.n_runs = 1; R.j_hi = 0; R.n_nodes = L - k + 1; R.n_seq = L;
-    R.words = (uint32_t)R.n_nodes + 1u + ((uint32_t)L + 3) / 4;
+    R.words = (uint32_t)R.n_nodes + 1u + ((uint32_t)L + 3) / 4 + ((LABELED && LP.P.labeled) ? 2u : 0u);
     return cls;
+}
+MGX_DEV int lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R) {
+    return LP.P.labeled ? lane_exact_t<true>(LP, read, R) : lane_exact_t<false>(LP, read, R);
 }
 
 // One read, as the host model calls it: the exact exit where it is on, else the DP.  (On the device the two are two kernels,

@@ -104,9 +104,12 @@ inline uint64_t lane_wave_scratch_bytes(uint32_t max_cols, uint64_t rest_stride)
 //  - xdrop >= 0: the cell that holds the best score so far never falls under the x-drop cut-off;
 //  - max_nodes_per_seq_char and max_ram_per_alignment need no condition: extend() tests them only for a column whose maximum is
 //    below the best score so far (aligner_extender_methods.cpp:521-547), which the all-match head never is;
-//  - not label-aware (the one-label bookkeeping of the lane reads rows column by column).
+//  - label-aware (labeled_flags: AlignParams::labeled): only with bit 1, no dummy node's row holds a label, as the lane itself.  The
+//    exit then takes the reads that keep one label all along: the one-label seed filter leaves a label L, and every node of the
+//    path has the row { L } (lane_exact_class(), DESIGN.md 3.4 "label-aware batches"); side branches carry a mismatch or a gap
+//    whatever their labels, so the argument above stands with { L } behind the alignment.
 inline bool lane_exact_config(const mgx_config &c, const DevConfig &d, uint32_t labeled_flags) {
-    if (labeled_flags & 1u) return false;
+    if ((labeled_flags & 1u) && !(labeled_flags & 2u)) return false;
     const char acgt[4] = { 'A', 'C', 'G', 'T' };
     const int m = c.score_matrix[(int)'A'][(int)'A'];
     for (int x = 0; x < 4; ++x)
@@ -117,6 +120,11 @@ inline bool lane_exact_config(const mgx_config &c, const DevConfig &d, uint32_t 
     if (c.xdrop < 0) return false;
     return true;
 }
+
+// whether the automatic default of the exact exit (option exact absent) extends to label-aware batches: decided by measurement —
+// four alternating pairs on BASELINE config 3 put the range with the exit wholly above the range without it
+// (profiles/r09_exact_labels_ab_pairs.txt; README.md, "And the label-aware batches")
+constexpr bool LANE_EXACT_AUTO_LABELED = true;
 
 // Whether the lane-per-read kernel may run in front of the group kernel for this configuration (every read it cannot finish
 // goes to the group kernel anyway; this only rules out configurations in which its shortcuts would not be exact or no read

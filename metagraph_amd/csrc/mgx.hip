@@ -328,8 +328,12 @@ static int plan_lane(mgx_aligner *A, AlignPlan &pl) {
     // seed spans the query; 2: also the path class), 0 turns it off; automatic: level 2 for the
     // batches the lane kernel takes of its own accord — a small batch run with lane=1 keeps every read's fate in lane_read_dp()
     // what the tests of its hand-over reasons pin.  (lane_enabled() filled the flag for the host model: decided here.)
-    LP.exact = (pl.lane_ok && A->opt.exact != 0 && lane_exact_config(A->cfg, A->dcfg, pl.labeled ? 1u : 0u)
-                && (A->opt.exact >= 1 || pl.n >= (uint64_t)pl.lane_blocks * 16)) ? (A->opt.exact >= 1 ? (uint32_t)A->opt.exact : 2u) : 0u;
+    // Label-aware batches (the reads that keep one label all along, lane_exact_class()): under the same rule, where no dummy
+    // node's row holds a label (lane_exact_config()); LANE_EXACT_AUTO_LABELED records that the automatic default includes them.
+    const uint32_t lflags = pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u;
+    const bool exact_auto = pl.n >= (uint64_t)pl.lane_blocks * 16 && (!pl.labeled || LANE_EXACT_AUTO_LABELED);
+    LP.exact = (pl.lane_ok && A->opt.exact != 0 && lane_exact_config(A->cfg, A->dcfg, lflags)
+                && (A->opt.exact >= 1 || exact_auto)) ? (A->opt.exact >= 1 ? (uint32_t)A->opt.exact : 2u) : 0u;
     pl.key_bits = work_key_bits(pl.n) + (LP.exact ? 1 : 0);
     LP.done_key = LP.exact ? 1u << work_key_bits(pl.n) : 0u;
     if (!pl.lane_ok) return MGX_OK;
@@ -624,7 +628,7 @@ static int exact_by_lanes(mgx_aligner *A, AlignPlan &pl) {
     LP.P.n_items = pl.n;
     HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)pl.cus * 4 * 8 * 4, (pl.n + 63) / 64);
-    if (int rc = mgx_launch_lane_exact(A->lane_params.p, blocks, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit: %d", rc);
+    if (int rc = mgx_launch_lane_exact(A->lane_params.p, blocks, pl.labeled ? 1 : 0, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit: %d", rc);
     unsigned long long done = 0;
     HIP_TRY(copy_sync(A, &done, cursor(A, CUR_LANE_DONE), 8, hipMemcpyDeviceToHost));      // (synchronises with the kernel)
     pl.n_exact = done;

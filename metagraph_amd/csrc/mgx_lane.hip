@@ -157,8 +157,11 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
 // of its own because k_lane has no register to spare — the same test inside its loop, in front of the DP, made the allocator
 // spill 33 VGPRs in the column loop, a mark tested where k_lane fetches its items cost 25 more spilled SGPRs there — and because
 // this way k_lane is the code it was: it never meets these reads.  One lane per read, in read order.
-__global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict__ LPp) {
-    const LaneParams &LP = *LPp;
+// Label-aware batches have a kernel of their own, k_lane_exact_labeled: the same loop around lane_exact_t<true>, whose filter over
+// the seeds' rows and scan over the path's rows (up to ~120 independent 8-byte gathers a read, four in flight at a time) take 30
+// registers more; k_lane_exact, compiled without them, keeps its code and its occupancy for the unlabeled batches.
+template <bool LABELED>
+__device__ __forceinline__ void lane_exact_body(const LaneParams &LP) {
     const int lane = (int)threadIdx.x;
     const uint64_t n_reads = LP.P.n_reads;
     LaneChip chip;
@@ -169,7 +172,7 @@ __global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict_
         LaneResult R;
         R.words = 0;
         LV<bool> hv;
-        const int cls = read < n_reads ? lane_exact(LP, read, R) : LANE_EXACT_NONE;
+        const int cls = read < n_reads ? lane_exact_t<LABELED>(LP, read, R) : LANE_EXACT_NONE;
         hv.v = cls != LANE_EXACT_NONE;
         if (!wave_ballot(hv)) continue;
         // output-stream words of the wavefront's reads: one atomic, a prefix sum over the lanes (as k_lane)
@@ -199,6 +202,9 @@ __global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict_
     }
 }
 
+__global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict__ LPp) { lane_exact_body<false>(*LPp); }
+__global__ void __launch_bounds__(64) k_lane_exact_labeled(const LaneParams *__restrict__ LPp) { lane_exact_body<true>(*LPp); }
+
 // blocks = resident wavefronts (wavefront b owns LaneParams::scratch + b * wave_stride)
 // d_params: the LaneParams of this launch in device memory
 extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream) {
@@ -207,8 +213,10 @@ extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stre
     return (int)hipGetLastError();
 }
 // the exact exit, between seeding and the work sort (LaneParams::exact; done_count and bail_hist start at zero and are k_lane's too)
-extern "C" int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, void *stream) {
-    k_lane_exact<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
+// labeled: the batch is label-aware (AlignParams::labeled != 0)
+extern "C" int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, int labeled, void *stream) {
+    if (labeled) k_lane_exact_labeled<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
+    else k_lane_exact<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     return (int)hipGetLastError();
 }
 extern "C" int mgx_lane_waves_per_simd(void) { return MGX_LANE_WAVES_PER_SIMD; }

@@ -43,6 +43,7 @@ def main():
     it = args.start
     n_reads_total = 0
     n_lane_total = 0
+    n_exact_total = 0
     sl_why = {}
     lab_hist = [0] * 12                  # --labels: reads by their number of alignments (0..5+), alignments by their number of labels
     while time.time() < t_end and not (args.worlds and it >= args.start + args.worlds):
@@ -244,6 +245,9 @@ def main():
             n_reads_total += len(reads)
             if args.lane:
                 n_lane_total += e.lane_stats()[1]
+                if os.environ.get("MGX_EMU_LANE_EXACT") in ("1", "2") and e.lane_stats()[0] and all(st == 0 for st in status):
+                    # (the exact exit: an alignment and no extension)
+                    n_exact_total += sum(1 for q, x in enumerate(e.seed_info()) if got[q] and x["n_extensions"] == 0)
             if args.seedlane:
                 ran, done, why = e.seedlane_stats()
                 n_lane_total += done
@@ -253,7 +257,7 @@ def main():
             print("MISMATCH", desc)
             print(str(ex)[:3000])
             sys.exit(1)
-    print("ok: %d worlds, %d reads, no difference" % (it, n_reads_total) + (" (%d reads finished by the lane path)" % n_lane_total if args.lane else "")
+    print("ok: %d worlds, %d reads, no difference" % (it, n_reads_total) + (" (%d reads finished by the lane path%s)" % (n_lane_total, ", %d of them through the exact exit" % n_exact_total if os.environ.get("MGX_EMU_LANE_EXACT") in ("1", "2") else "") if args.lane else "")
           + (" (%d reads seeded by the lane-per-read seeder; left by reason: %s)" % (n_lane_total, dict(sorted(sl_why.items()))) if args.seedlane else "")
           + (" (reads with 0..5+ alignments: %s; alignments with 0..5+ labels: %s)" % (lab_hist[:6], lab_hist[6:]) if args.labels else ""))
 

@@ -51,6 +51,7 @@ while time.time() - t0 < 60 * minutes:
             assert got[q] == want[q], ("MISMATCH", seed, q, reads[q], got[q], want[q])
         st = A.stats()
         worlds += 1; reads_total += len(reads); lane_total += st["n_lane_reads"]
+        exact_total += st["n_lane_exact_reads"] + st["n_lane_exact_path_reads"]
         A.close()
         seed += 1
         continue

@@ -3,6 +3,8 @@
 oracle's LabeledAligner: segment-labelled worlds (tests/test_lane_labels.py::segment_world) with random k, read length, SNP
 density, label count and configuration; alignments, label lists, the label filter's seed lists and num_matching of every read.
     python tools/fuzz_lane_labels.py N_WORLDS [FIRST_SEED]
+With MGX_EMU_LANE_EXACT=1 / 2 in the environment the lane's exact exit is on at that level (lane_read.hpp lane_exact()); the reads
+that left through it — an alignment and no extension — are counted.
 CPU only (test infrastructure)."""
 import os, sys, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +15,7 @@ import emu_drv, orc
 from metagraph_amd import capi
 from labeled_worlds import with_labels
 from test_lane_labels import segment_world
-tot = done_t = bad_t = sl_t = 0
+tot = done_t = bad_t = sl_t = exact_t = 0
 first = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 for seed in range(first, first + int(sys.argv[1])):
     rng = random.Random(seed)
@@ -37,5 +39,7 @@ for seed in range(first, first + int(sys.argv[1])):
     ran, nd = e.lane_stats()
     sl_t += e.seedlane_stats()[1]
     tot += len(reads); done_t += nd; bad_t += len(bad)
+    if ran: exact_t += sum(1 for q in range(len(reads)) if got[q] and info[q]["n_extensions"] == 0)
     if bad: print("seed", seed, "k", k, "BAD", bad[:5])
-print("worlds done: reads", tot, "seeded by the lane-per-read seeder", sl_t, "lane finished", done_t, "mismatches", bad_t)
+print("worlds done: reads", tot, "seeded by the lane-per-read seeder", sl_t, "lane finished", done_t,
+      "through the exact exit", exact_t, "mismatches", bad_t)
