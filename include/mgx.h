@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 6      /* still 6: symbols added only: mgx_annotation_load_columns_device / mgx_column_file_decode_device / mgx_column_decode_kernel_launch_counts
+#define MGX_ABI_VERSION 6      /* still 6: symbols added only: mgx_column_coord_file_read / mgx_column_file_coord_begin / mgx_column_file_coords /
+                                * mgx_annotation_set_coordinates_device / mgx_annotation_load_coord_columns_device / mgx_column_coord_file_decode_device
+                                * (k-mer coordinates read from files, on the host and on the device); before that mgx_annotation_load_columns_device / mgx_column_file_decode_device / mgx_column_decode_kernel_launch_counts
                                 * (`.column.annodbg` files decoded by kernels); before that mgx_stats::n_lane_exact_reads and (later) n_lane_exact_path_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
                                 * header) and the option exact; before that, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
                                 * (the mgx_results layout of a batch, written by kernels); before that mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
@@ -496,7 +498,11 @@ size_t mgx_format_json(const mgx_results *res, uint64_t query_index, const char 
  * whose rows ARE the label sets AnnotationBuffer would fetch, plus the batched BinaryMatrix::get_rows of
  * AnnotationBuffer::fetch_queued_annotations as an entry point of its own (annotation_buffer.cpp:182; ColumnMajor::get_rows,
  * annotation/binary_matrix/column_sparse/column_major.cpp:27-44 — 1000 columns x |rows| random bit tests in the reference).
- * Not built: label coordinates and seed chaining (aligner_labeled.cpp:361-448,685-700, aligner_chainer.cpp:47-339).
+ * Label coordinates: read from `.column.annodbg.coords` / `.column_coord.annodbg` files on the host and on the device
+ * (mgx_column_coord_file_read, mgx_annotation_load_coord_columns_device, "files" below), kept row-major on the device and answered by
+ * mgx_annotation_get_row_tuples; the anchor DP of seed chaining is mgx_chain_seeds.  Not built: LabeledAligner's coordinate mode
+ * itself, i.e. the extension half of chaining (aligner_labeled.cpp:361-448,685-700, aligner_chainer.cpp:47-339) — an annotation
+ * with coordinates is refused by mgx_labeled_aligner_create.
  *
  * mgx_annotation_create stands in for the annotator argument of LabeledAligner<>(graph, config, annotator)
  * (aligner_labeled.hpp:125-127): the binary matrix as column bit vectors, columns[j] = ceil(n_rows / 64) words, bit r =
@@ -532,6 +538,11 @@ int mgx_annotation_get_rows(mgx_annotation *a, const uint64_t *rows, uint64_t n,
  * aligner_labeled.cpp:457-462) is not — mgx_labeled_aligner_create refuses such an annotation (MGX_ERR_UNSUPPORTED). */
 int mgx_annotation_set_coordinates(mgx_annotation *a, uint32_t n_labels, const uint64_t *col_begin, const uint64_t *rows,
                                    const uint64_t *coord_begin, const int64_t *coords);
+/* The same with rows, coord_begin and coords in device memory (col_begin stays a host array); the row-major form is built by
+ * kernels: the same tables, and for a row outside the matrix or a descending tuple the same code and message.  The
+ * number of launches and allocations does not depend on n_labels. */
+int mgx_annotation_set_coordinates_device(mgx_annotation *a, uint32_t n_labels, const uint64_t *col_begin, const uint64_t *rows,
+                                          const uint64_t *coord_begin, const int64_t *coords);
 int mgx_annotation_has_coordinates(const mgx_annotation *a);
 int mgx_annotation_get_row_tuples(mgx_annotation *a, const uint64_t *rows, uint64_t n, uint64_t *out_begin, uint32_t *out_labels,
                                   uint64_t label_cap, uint64_t *out_coord_begin, int64_t *out_coords, uint64_t coord_cap,
@@ -785,7 +796,23 @@ uint32_t mgx_column_file_num_labels(const mgx_column_file *f);
 const char *mgx_column_file_label(const mgx_column_file *f, uint32_t j);      /* LabelEncoder::decode(j) */
 const uint64_t *mgx_column_file_col_begin(const mgx_column_file *f);          /* num_labels + 1 entries */
 const uint64_t *mgx_column_file_rows(const mgx_column_file *f);               /* the arguments of mgx_annotation_create_sparse */
+/* An object of mgx_column_coord_file_read: mgx_annotation_set_coordinates is called with its coordinates as well. */
 int mgx_annotation_create_from_file(const mgx_column_file *f, int device, mgx_annotation **out);
+/* Column annotations with k-mer coordinates (annot::ColumnCoordAnnotator), in either of the two forms the reference writes:
+ *   (a) `X.column.annodbg` + the side file `X.column.annodbg.coords` next to it (`metagraph annotate --coordinates`; the side file:
+ *       per column a bit_vector_smart of delimiters and an sdsl::int_vector<> of values, TupleCSCMatrix::serialize_tuples); several
+ *       such pairs side by side as in mgx_column_file_read, a label in two files: MGX_ERR_UNSUPPORTED; a missing side file:
+ *       MGX_ERR_INVALID naming its path;
+ *   (b) one `X.column_coord.annodbg` (a path with that ending; it must be the only path): label encoder, ColumnMajor (bit_vector_sd
+ *       columns without a representation code; the row count is the columns' common size), then the same tuple section.
+ * Checked per column, in this order: the delimiter vector (values + set rows + 1 bits, set rows + 1 of them set, the first and the
+ * last among them), every value below 2^63, every tuple ascending; then that no bytes follow the last column.  Each fault:
+ * MGX_ERR_INVALID with the field named in mgx_last_error.  The object answers the accessors above and the two below: coords of
+ * matrix entry x (rows[x]) = coords[coord_begin[x] .. coord_begin[x + 1]), the arguments of mgx_annotation_set_coordinates.
+ * Both return NULL on an object of mgx_column_file_read (which ignores side files) and on a names_out. */
+int mgx_column_coord_file_read(const char *const *paths, uint32_t n_paths, mgx_column_file **out);
+const uint64_t *mgx_column_file_coord_begin(const mgx_column_file *f);        /* col_begin[num_labels] + 1 entries */
+const int64_t *mgx_column_file_coords(const mgx_column_file *f);
 /* mgx_column_file_read + mgx_annotation_create_from_file with the columns decoded by kernels: same contract, the
  * same annotation (mgx_annotation_get_rows answers alike), the same error codes and messages for the same files.  The host reads
  * the files and walks their headers (num_rows, the label encoder, per column the representation code and the container headers);
@@ -801,8 +828,18 @@ int mgx_annotation_load_columns_device(const char *const *paths, uint32_t n_path
 /* Test hook: the same kernels, then the rows copied back into a host-owned mgx_column_file — what mgx_column_file_read returns,
  * entry for entry. */
 int mgx_column_file_decode_device(const char *const *paths, uint32_t n_paths, int device, mgx_column_file **out);
-/* Test hook: out4 = kernel launches, device allocations, bytes copied host-to-device, bytes copied device-to-host by the two calls
- * above — since the library was loaded (the copies inside mgx_annotation_create_sparse are not counted). */
+/* mgx_column_coord_file_read + mgx_annotation_create_from_file with everything decoded by kernels, under the contract
+ * of mgx_annotation_load_columns_device: the delimiter vectors (in whichever of sd / inverted sd / stat / rrr they are stored) and
+ * the values' raw words go up with the binary columns in the same single copy; kernels decode the delimiters to bit maps, rank
+ * them into coord_begin, unpack the values (widths 1 to 64) into coords, and mgx_annotation_set_coordinates_device transposes them.
+ * No row index and no coordinate is copied to the host; launches and allocations do not depend on the number of columns; on any
+ * fault the host reader runs on the same files and ITS code and message are returned. */
+int mgx_annotation_load_coord_columns_device(const char *const *paths, uint32_t n_paths, int device, mgx_annotation **out, mgx_column_file **names_out);
+/* Test hook: the same kernels, then rows, coord_begin and coords copied back into a host-owned mgx_column_file — what
+ * mgx_column_coord_file_read returns, entry for entry. */
+int mgx_column_coord_file_decode_device(const char *const *paths, uint32_t n_paths, int device, mgx_column_file **out);
+/* Test hook: out4 = kernel launches, device allocations, bytes copied host-to-device, bytes copied device-to-host by the four calls
+ * above — since the library was loaded (the copies inside mgx_annotation_create_sparse / _set_coordinates_device are not counted). */
 void mgx_column_decode_kernel_launch_counts(uint64_t *out4);
 
 #ifdef __cplusplus

@@ -55,14 +55,17 @@ def read_edgemask(path, state, n_edges):
     return out
 
 
-def read_column_files(paths, on_device=False, device=0):
+def read_column_files(paths, on_device=False, device=0, coordinates=False):
     """mgx_column_file_read (host only): (n_rows, label names, col_begin, rows) of one or several `.column.annodbg` files.
     on_device: mgx_column_file_decode_device, the same content decoded by the kernels of mgx_annotation_load_columns_device and
-    copied back."""
+    copied back.  coordinates: mgx_column_coord_file_read / mgx_column_coord_file_decode_device over `.column.annodbg` files with
+    their `.coords` side files, or one `.column_coord.annodbg`; the tuple grows by (coord_begin, coords)."""
     L = capi.lib()
     arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
     h = C.c_void_p()
-    if on_device:
+    if coordinates:
+        _check((L.mgx_column_coord_file_decode_device(arr, len(paths), device, C.byref(h)) if on_device else L.mgx_column_coord_file_read(arr, len(paths), C.byref(h))))
+    elif on_device:
         _check(L.mgx_column_file_decode_device(arr, len(paths), device, C.byref(h)))
     else:
         _check(L.mgx_column_file_read(arr, len(paths), C.byref(h)))
@@ -71,6 +74,10 @@ def read_column_files(paths, on_device=False, device=0):
         names = [L.mgx_column_file_label(h, j).decode() for j in range(n)]
         cb = np.ctypeslib.as_array(L.mgx_column_file_col_begin(h), shape=(n + 1,)).copy()
         rows = np.ctypeslib.as_array(L.mgx_column_file_rows(h), shape=(int(cb[-1]),)).copy() if int(cb[-1]) else np.zeros(0, dtype=np.uint64)
+        if coordinates:
+            cob = np.ctypeslib.as_array(L.mgx_column_file_coord_begin(h), shape=(int(cb[-1]) + 1,)).copy()
+            co = np.ctypeslib.as_array(L.mgx_column_file_coords(h), shape=(int(cob[-1]),)).copy() if int(cob[-1]) else np.zeros(0, dtype=np.int64)
+            return int(L.mgx_column_file_num_rows(h)), names, cb, rows, cob, co
         return int(L.mgx_column_file_num_rows(h)), names, cb, rows
     finally:
         L.mgx_column_file_free(h)
@@ -167,18 +174,35 @@ class Annotation:
         return self
 
     @classmethod
-    def load(cls, paths, device=0, on_device=False):
+    def load(cls, paths, device=0, on_device=False, coordinates=False):
         """`.column.annodbg` files written by the reference (ColumnCompressed::load / merge_load); label names in .labels.
-        on_device: mgx_annotation_load_columns_device, the columns decoded by kernels (the same annotation)."""
+        on_device: mgx_annotation_load_columns_device, the columns decoded by kernels (the same annotation).
+        coordinates: the files' k-mer coordinates too (`.coords` side files, or one `.column_coord.annodbg`):
+        mgx_column_coord_file_read + mgx_annotation_create_from_file, or mgx_annotation_load_coord_columns_device on_device."""
         if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
             paths = [paths]
+        L = capi.lib()
+        if coordinates and not on_device:
+            arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+            f = C.c_void_p()
+            _check(L.mgx_column_coord_file_read(arr, len(paths), C.byref(f)))
+            try:
+                self = cls.__new__(cls)
+                self.h = C.c_void_p()
+                self._cols = []
+                _check(L.mgx_annotation_create_from_file(f, device, C.byref(self.h)))
+                self.n_rows, self.n_labels = int(L.mgx_column_file_num_rows(f)), int(L.mgx_column_file_num_labels(f))
+                self.labels = [L.mgx_column_file_label(f, j).decode() for j in range(self.n_labels)]
+            finally:
+                L.mgx_column_file_free(f)
+            return self
         if on_device:
-            L = capi.lib()
             arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
             self = cls.__new__(cls)
             self.h, names = C.c_void_p(), C.c_void_p()
             self._cols = []
-            _check(L.mgx_annotation_load_columns_device(arr, len(paths), device, C.byref(self.h), C.byref(names)))
+            load = L.mgx_annotation_load_coord_columns_device if coordinates else L.mgx_annotation_load_columns_device
+            _check(load(arr, len(paths), device, C.byref(self.h), C.byref(names)))
             try:
                 self.n_rows, self.n_labels = int(L.mgx_column_file_num_rows(names)), int(L.mgx_column_file_num_labels(names))
                 self.labels = [L.mgx_column_file_label(names, j).decode() for j in range(self.n_labels)]
@@ -193,6 +217,34 @@ class Annotation:
     @property
     def device_bytes(self):
         return capi.lib().mgx_annotation_device_bytes(self.h)
+
+    def has_coordinates(self):
+        """AnnotationBuffer::has_coordinates: the annotation carries k-mer coordinates"""
+        return bool(capi.lib().mgx_annotation_has_coordinates(self.h))
+
+    def get_row_tuples(self, rows):
+        """mgx_annotation_get_row_tuples (MultiIntMatrix::get_row_tuples): per requested row its [(label, [coordinates])], labels
+        ascending; a row outside the matrix has none."""
+        L = capi.lib()
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        n = len(rows)
+        begin = np.zeros(n + 1, dtype=np.uint64)
+        u64p, i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+        ptr = lambda a, t: a.ctypes.data_as(t)
+        label_cap, coord_cap = max(16, 2 * n), max(16, 4 * n)
+        while True:
+            labels = np.zeros(label_cap, dtype=np.uint32)
+            cbegin = np.zeros(label_cap + 1, dtype=np.uint64)
+            coords = np.zeros(coord_cap, dtype=np.int64)
+            nl, nc = C.c_uint64(), C.c_uint64()
+            rc = L.mgx_annotation_get_row_tuples(C.c_void_p(self.h.value), ptr(rows, u64p), C.c_uint64(n), ptr(begin, u64p), ptr(labels, C.POINTER(C.c_uint32)),
+                                                 C.c_uint64(label_cap), ptr(cbegin, u64p), ptr(coords, i64p), C.c_uint64(coord_cap), C.byref(nl), C.byref(nc))
+            if rc == capi.MGX_ERR_CAPACITY and (nl.value > label_cap or nc.value > coord_cap):
+                label_cap, coord_cap = max(label_cap, nl.value), max(coord_cap, nc.value)
+                continue
+            _check(rc)
+            break
+        return [[(int(labels[e]), coords[int(cbegin[e]):int(cbegin[e + 1])].tolist()) for e in range(int(begin[i]), int(begin[i + 1]))] for i in range(n)]
 
     def close(self):
         if getattr(self, "h", None) and capi is not None:

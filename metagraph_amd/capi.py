@@ -256,6 +256,13 @@ def lib():
     L.mgx_annotation_create_from_file.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_annotation_load_columns_device.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.mgx_column_file_decode_device.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.mgx_column_coord_file_read.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.mgx_column_file_coord_begin.argtypes = [C.c_void_p]
+    L.mgx_column_file_coord_begin.restype = C.POINTER(C.c_uint64)
+    L.mgx_column_file_coords.argtypes = [C.c_void_p]
+    L.mgx_column_file_coords.restype = C.POINTER(C.c_int64)
+    L.mgx_annotation_load_coord_columns_device.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mgx_column_coord_file_decode_device.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_column_decode_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.mgx_column_decode_kernel_launch_counts.restype = None
     L.mgx_graph_create.argtypes = [C.POINTER(BossView), C.c_int, C.POINTER(C.c_void_p)]

@@ -1,6 +1,7 @@
 // Readers of the reference's own files: `.dbg` (DBGSuccinct::load_without_mask, dbg_succinct.cpp:690-711
 // over BOSS::load, boss.cpp:338-394) and `.column.annodbg` (ColumnCompressed::load, annotate_column_compressed.cpp:436-481).
 // Host code only; the decoded W / last / F and the columns' set rows go to mgx_graph_create / mgx_annotation_create_sparse.
+// Also the k-mer coordinates of column annotations (`.column.annodbg.coords` side files, `.column_coord.annodbg`; at the end).
 //
 // The reference serialises its vectors with sdsl-lite, an empty submodule under /root/reference: the container layouts below
 // are restated from sdsl-lite's published serialisation (`serialize()` of int_vector, rrr_vector, sd_vector, wt_pc + byte_tree,
@@ -376,6 +377,11 @@ struct ColumnFile {
     uint64_t n_rows = 0;
     std::vector<std::string> labels;
     std::vector<uint64_t> col_begin{ 0 }, rows;     // rows[col_begin[j] .. col_begin[j + 1]): the set rows of column j, ascending
+    // k-mer coordinates (read_tuples: mgx_column_coord_file_read only), laid out as mgx_annotation_set_coordinates takes them:
+    // matrix entry x (rows[x] under its column's label) has coords[coord_begin[x] .. coord_begin[x + 1])
+    bool has_coords = false;
+    std::vector<uint64_t> coord_begin;              // rows.size() + 1 entries
+    std::vector<int64_t> coords;
 };
 
 inline std::string read_short_string(Cursor &c) {   // load_string, serialization.cpp:235-256: UTF-8 coded length, bytes
@@ -455,6 +461,95 @@ inline ColumnFile parse_columns(const uint8_t *data, size_t n) {
 inline ColumnFile read_columns(const std::string &path) {
     const std::vector<uint8_t> buf = read_whole_file(path);
     return parse_columns(buf.data(), buf.size());
+}
+
+// ---- k-mer coordinates ------------------------------------------------------------------------------------------------------------
+// The tuple section (TupleCSCMatrix::load_tuples / serialize_tuples, annotation/int_matrix/rank_extended/tuple_csc_matrix.hpp:
+// 155-180): per column, in column order, a bit_vector_smart of delimiters (read_adaptive) and an sdsl::int_vector<> of values.
+// The tuple of the column's set row of rank r (1-based) is values[select1(r) + 1 - r .. select1(r + 1) - r) (:116-125), so a
+// well-formed delimiter vector has n_values + n_set + 1 bits, n_set + 1 of them set, the first and the last among them
+// (the writer: annotate_column_compressed.cpp:320-337, :352-406).  Two adjacent ones are an empty tuple.
+// Columns first .. first + n of f (their set rows are in f already); appends to f.coord_begin / f.coords.
+inline void read_tuples(Cursor &c, ColumnFile &f, size_t first, size_t n) {
+    if (f.coord_begin.empty()) f.coord_begin.push_back(0);
+    for (size_t j = first; j < first + n; ++j) {
+        const uint64_t n_set = f.col_begin[j + 1] - f.col_begin[j];
+        uint64_t sd_size = 0;
+        {   // an sd_vector's length field is bounded by nothing else in the file: at most one bit per value bit that can follow
+            Cursor peek = c;
+            if (peek.be("delimiters") == CODE_SD) {
+                sd_size = peek.le("delimiters");
+                if (sd_size > (uint64_t)c.left() * 8 + n_set + 1) throw ParseError("delimiters: size field exceeds the file");
+            }
+        }
+        const Bits d = read_adaptive(c, "delimiters", sd_size);
+        const Bits v = read_int_vector(c, "values");
+        const uint64_t n_values = v.size();
+        if (d.bits != n_values + n_set + 1)
+            throw ParseError("delimiters: " + std::to_string(d.bits) + " bits for " + std::to_string(n_values) + " values of " + std::to_string(n_set) + " set rows");
+        uint64_t ones = 0;
+        for (uint64_t wi = 0; wi + 1 < d.w.size(); ++wi) {
+            uint64_t x = d.w[wi];
+            if ((wi + 1) * 64 > d.bits) x &= (d.bits & 63) ? (1ull << (d.bits & 63)) - 1 : 0;
+            ones += (uint64_t)__builtin_popcountll(x);
+        }
+        if (ones != n_set + 1) throw ParseError("delimiters: " + std::to_string(ones) + " set bits, the column has " + std::to_string(n_set) + " set rows");
+        if (!d.bit(0)) throw ParseError("delimiters: first bit clear");
+        if (!d.bit(d.bits - 1)) throw ParseError("delimiters: last bit clear");
+        const uint64_t base = f.coords.size();
+        for (uint64_t i = 0; i < n_values; ++i) {
+            const uint64_t x = v.at(i);
+            if (x >> 63) throw ParseError("values: a coordinate of 2^63 or more");
+            f.coords.push_back((int64_t)x);
+        }
+        uint64_t i = 0;                              // the one of rank i + 1 at position p: its tuple begins at value p - i
+        for (uint64_t wi = 0; wi + 1 < d.w.size(); ++wi)
+            for (uint64_t x = d.w[wi]; x; x &= x - 1) {
+                const uint64_t p = wi * 64 + (uint64_t)__builtin_ctzll(x);
+                if (p >= d.bits) break;
+                if (i) f.coord_begin.push_back(base + p - i);
+                ++i;
+            }
+        for (uint64_t e = f.col_begin[j]; e < f.col_begin[j + 1]; ++e)
+            for (uint64_t t = f.coord_begin[e] + 1; t < f.coord_begin[e + 1]; ++t)
+                if (f.coords[t] < f.coords[t - 1]) throw ParseError("coordinates: a tuple is not ascending");
+    }
+    if (c.left()) throw ParseError("bytes left after the last column");
+    f.has_coords = true;
+}
+
+// Form (a): `X.column.annodbg` (parse_columns) plus its side file `X.column.annodbg.coords` (ColumnCompressed<>::kCoordExtension,
+// what `metagraph annotate --coordinates` writes): the tuple section alone, its columns in the order of the column file's label
+// encoder (load_coords, annotation_converters.cpp:1701-1742) — read_tuples over the side file's image.
+
+// Form (b): `X.column_coord.annodbg`, ColumnCoordAnnotator = StaticBinRelAnnotator<TupleCSCMatrix<ColumnMajor>>
+// (static_annotators_def.hpp:64,108): the label encoder (annotation_matrix.cpp:25-56), ColumnMajor::serialize
+// (column_major.cpp:87-123: serialize_number(n_columns), then one bit_vector_sd per column — an sd_vector and the inverted byte,
+// NO representation code), the tuple section.  No num_rows field: the row count is the columns' common size.
+inline ColumnFile parse_column_coord(const uint8_t *data, size_t n) {
+    Cursor c(data, n);
+    ColumnFile f;
+    read_label_encoder(c, data, f.labels);
+    const uint64_t n_cols = c.be("number of columns");
+    if (n_cols != f.labels.size()) throw ParseError("number of columns: " + std::to_string(n_cols) + ", the label encoder has " + std::to_string(f.labels.size()) + " labels");
+    for (uint64_t j = 0; j < n_cols; ++j) {
+        uint64_t size;
+        { Cursor peek = c; size = peek.le("column"); }
+        if (!j) {
+            if (size >= (1ull << 40)) throw ParseError("more rows than the device matrix addresses (2^40)");
+            f.n_rows = size;
+        } else if (size != f.n_rows) throw ParseError("inconsistent column size");
+        std::vector<uint64_t> ones;
+        read_sd_vector(c, "column", f.n_rows, [&](uint64_t p) { ones.push_back(p); });
+        if (c.u8("column")) {                        // (as parse_columns)
+            if (size > (1ull << 33) || f.rows.size() + size > (1ull << 33)) throw Unsupported("column: inverted column of more than 2^33 rows");
+            size_t q = 0;
+            for (uint64_t r = 0; r < size; ++r) { if (q < ones.size() && ones[q] == r) ++q; else f.rows.push_back(r); }
+        } else f.rows.insert(f.rows.end(), ones.begin(), ones.end());
+        f.col_begin.push_back(f.rows.size());
+    }
+    read_tuples(c, f, 0, f.labels.size());
+    return f;
 }
 
 }}  // namespace mgx::files

@@ -100,15 +100,13 @@ MGX_HD uint64_t cd_high_popcount(const uint64_t *arena, const CdSd *sd, const ui
 // to rows[col_begin[label] + i].  hrank: the scan of cd_high_popcount.
 // Order: p rises with i, so the upper parts p - i never fall, and two positions can be out of order only where the upper parts
 // are equal, which is where bit p - 1 of high is set as well: then, and only then, low[i] must exceed low[i - 1].
-MGX_HD void cd_sd_word(uint64_t *arena, const CdSd *sd, const uint64_t *hprefix, uint32_t n_sd, const uint64_t *hrank, uint64_t gw,
-                       uint64_t n_rows, int pass, const uint64_t *col_begin, uint64_t *rows, uint64_t *err) {
-    const uint32_t s = cd_find(hprefix, n_sd, gw);
-    const CdSd d = sd[s];
-    if ((d.inverted != 0) != (pass == 0)) return;
-    const uint64_t lw = gw - hprefix[s];
+// (cd_sd_each: the walk over one word's set bits with the checks, shared with the delimiter vectors of coord_decode.hpp, whose
+// sizes differ per column; sink(i, v): the i-th position v of the column, false to stop)
+template <class Sink>
+MGX_HD void cd_sd_each(const uint64_t *arena, const CdSd &d, uint64_t lw, uint64_t i, uint64_t size, uint64_t *err, Sink &&sink) {
     const uint64_t *high = arena + d.high_begin, *low = arena + d.low_begin;
     const uint64_t word = dd_word_masked(high, lw, d.high_bits);
-    uint64_t x = word, i = hrank[gw] - hrank[hprefix[s]];
+    uint64_t x = word;
     const uint64_t before = lw ? high[lw - 1] >> 63 : 0;                // bit p - 1 of the word's first bit
     for (unsigned t = 0; t < 64 && x; ++t, ++i, x &= x - 1) {
         if (i >= d.ones || i >= d.low_n) { cd_fail(err, d.label, CD_SD_SELECT, i); return; }
@@ -118,19 +116,31 @@ MGX_HD void cd_sd_word(uint64_t *arena, const CdSd *sd, const uint64_t *hprefix,
         if (d.wl && (up >> (64 - d.wl))) { cd_fail(err, d.label, CD_SD_SHIFT, i); return; }
         const uint64_t v = (up << d.wl) | lo;
         const bool adjacent = b ? (word >> (b - 1)) & 1 : before != 0;
-        if (v >= n_rows || (i && adjacent && lo <= (d.wl ? dd_get(low, (i - 1) * d.wl, d.wl) : 0))) { cd_fail(err, d.label, CD_SD_ORDER, i); return; }
-        if (pass == 0) {
+        if (v >= size || (i && adjacent && lo <= (d.wl ? dd_get(low, (i - 1) * d.wl, d.wl) : 0))) { cd_fail(err, d.label, CD_SD_ORDER, i); return; }
+        if (!sink(i, v)) return;
+    }
+}
+MGX_HD void cd_set_bit(uint64_t *word, unsigned bit) {
 #if defined(__HIP_DEVICE_COMPILE__)
-            atomicOr(reinterpret_cast<unsigned long long *>(arena + d.bm_begin + (v >> 6)), 1ull << (v & 63));
+    atomicOr(reinterpret_cast<unsigned long long *>(word), 1ull << bit);
 #else
-            arena[d.bm_begin + (v >> 6)] |= 1ull << (v & 63);
+    *word |= 1ull << bit;
 #endif
-        } else {
+}
+MGX_HD void cd_sd_word(uint64_t *arena, const CdSd *sd, const uint64_t *hprefix, uint32_t n_sd, const uint64_t *hrank, uint64_t gw,
+                       uint64_t n_rows, int pass, const uint64_t *col_begin, uint64_t *rows, uint64_t *err) {
+    const uint32_t s = cd_find(hprefix, n_sd, gw);
+    const CdSd d = sd[s];
+    if ((d.inverted != 0) != (pass == 0)) return;
+    cd_sd_each(arena, d, gw - hprefix[s], hrank[gw] - hrank[hprefix[s]], n_rows, err, [&](uint64_t i, uint64_t v) {
+        if (pass == 0) cd_set_bit(arena + d.bm_begin + (v >> 6), (unsigned)(v & 63));
+        else {
             const uint64_t o = col_begin[d.label] + i;
-            if (o >= col_begin[d.label + 1]) { cd_fail(err, d.label, CD_OUT_RANGE, i); return; }
+            if (o >= col_begin[d.label + 1]) { cd_fail(err, d.label, CD_OUT_RANGE, i); return false; }
             rows[o] = v;
         }
-    }
+        return true;
+    });
 }
 
 // ---- bit-map columns: word g = t * W + w of bit-map column t ----------------------------------------------------------------------

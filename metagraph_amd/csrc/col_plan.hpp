@@ -21,6 +21,8 @@ struct NeedsHost : std::runtime_error { using std::runtime_error::runtime_error;
 struct ColumnPlan { uint64_t code = CODE_SD; SdPlan sd; StatPlan stat; RrrPlan rrr; };
 struct ColumnsPlan {
     uint64_t n_rows = 0;
+    bool coded = true;                           // every column begins with a representation code (false: the bare bit_vector_sd
+                                                 // columns of a `.column_coord.annodbg`, coord_plan.hpp)
     std::vector<std::string> labels;
     std::vector<ColumnPlan> cols;
 };
@@ -69,13 +71,15 @@ struct ColBatch {
     std::vector<uint32_t> file_first;             // the first label of every file
     std::vector<uint64_t> stage;                  // the uploaded part of the arena
     uint64_t upload_words = 0, arena_words = 0;
+    uint64_t extra_begin = 0;                     // the first of the `extra_upload` words of build()
     bool kinds[4] = { false, false, false, false };
     uint64_t high_words() const { return hprefix.back(); }
     uint64_t bm_words() const { return (uint64_t)bm.size() * W; }
     uint64_t rrr_blocks() const { return (uint64_t)rrr.size() * n_blocks; }
 
     // plans[f] over images that outlive the call.  n_rows > 0 (an empty matrix has nothing to decode).
-    void build(const std::vector<ColumnsPlan> &plans) {
+    // extra_upload: words kept free (zero) at the end of the uploaded part for payloads of the caller's (coord_plan.hpp)
+    void build(const std::vector<ColumnsPlan> &plans, uint64_t extra_upload = 0) {
         n_rows = plans[0].n_rows;
         W = (n_rows + 63) / 64;
         n_blocks = (n_rows + 62) / 63;
@@ -127,6 +131,8 @@ struct ColBatch {
         section([](const ColumnPlan &c) { return c.code == CODE_SD ? &c.sd.low : nullptr; }, [&](uint32_t j, uint64_t o) { sd[lab[j].sd].low_begin = o; });
         section([](const ColumnPlan &c) { return c.code == CODE_SD ? &c.sd.high : nullptr; }, [&](uint32_t j, uint64_t o) { sd[lab[j].sd].high_begin = o; });
         section([](const ColumnPlan &c) { return c.code == CODE_STAT ? &c.stat.v : nullptr; }, [&](uint32_t j, uint64_t o) { bm[lab[j].bm].src_begin = o; });
+        extra_begin = at;
+        at += extra_upload;
         upload_words = at;
         stage.assign(upload_words, 0);
         auto copy = [&](const RawVec &v, uint64_t o) { if (v.words()) memcpy(stage.data() + o, v.src, v.words() * 8); };

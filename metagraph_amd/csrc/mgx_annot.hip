@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/mgx.h"
+#include "coord_decode.hpp"
 #include "kernel_units.hpp"
 
 namespace {
@@ -151,6 +152,33 @@ __global__ void k_pairs_fill(const uint64_t *keys, uint64_t n_pairs, uint64_t n_
     if (c < 2) return;
     for (uint32_t x = 0; x < c; ++x) more[offset[row] + x] = (uint32_t)(keys[p + x] & 0xFFFFFF);      // ascending: the keys are sorted
 }
+// ---- the transposition of coordinates (mgx_annotation_set_coordinates_device); bodies: coord_decode.hpp ----
+using namespace mgx;
+__global__ void __launch_bounds__(256) k_ct_check(const uint64_t *rows, uint64_t n_entries, uint64_t n_rows, const uint64_t *coord_begin,
+                                                  const int64_t *coords, uint64_t n_coords, uint64_t n_items, uint64_t *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_items) ct_check(rows, n_entries, n_rows, coord_begin, coords, n_coords, i, err);
+}
+__global__ void __launch_bounds__(256) k_ct_keys(const uint64_t *col_begin, uint32_t n_labels, const uint64_t *rows, uint64_t n_entries, uint64_t n_rows,
+                                                 uint64_t *keys, uint64_t *perm) {
+    const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < n_entries) ct_key(col_begin, n_labels, rows, n_rows, x, keys, perm);
+}
+__global__ void __launch_bounds__(256) k_ct_row_count(const uint64_t *keys, uint64_t n_entries, uint64_t n_rows, uint64_t *len) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n_entries) ct_row_count(keys, n_entries, n_rows, e, len);
+}
+__global__ void __launch_bounds__(256) k_ct_tuple_len(const uint64_t *perm, const uint64_t *coord_begin, uint64_t n_entries, uint64_t n_coords, uint64_t *tlen) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e <= n_entries) tlen[e] = ct_tuple_len(perm, coord_begin, n_entries, n_coords, e);
+}
+__global__ void __launch_bounds__(256) k_ct_copy(const uint64_t *coord_off, const uint64_t *perm, const uint64_t *coord_begin, const int64_t *coords,
+                                                 uint64_t n_entries, uint64_t n_coords, uint64_t total, int64_t *out) {
+    const uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o < total) ct_copy(coord_off, perm, coord_begin, coords, n_entries, n_coords, o, out);
+}
+const char *const MSG_COORD_ROW = "mgx_annotation_set_coordinates: a row index is outside the matrix";
+const char *const MSG_COORD_ORDER = "mgx_annotation_set_coordinates: coordinates must be ascending";
 } // namespace
 
 // get_row_tuples: per requested row and label, the number of its coordinates, then the coordinates themselves
@@ -429,7 +457,7 @@ int mgx_annotation_set_coordinates(mgx_annotation *a, uint32_t n_labels, const u
     order.reserve(n_pairs);
     for (uint32_t j = 0; j < n_labels; ++j)
         for (uint64_t x = col_begin[j]; x < col_begin[j + 1]; ++x) {
-            if (rows[x] >= a->n_rows) return afail(MGX_ERR_INVALID, "mgx_annotation_set_coordinates: a row index is outside the matrix");
+            if (rows[x] >= a->n_rows) return afail(MGX_ERR_INVALID, "%s", MSG_COORD_ROW);
             order.push_back({ { rows[x], j }, x });
         }
     std::sort(order.begin(), order.end());
@@ -440,7 +468,7 @@ int mgx_annotation_set_coordinates(mgx_annotation *a, uint32_t n_labels, const u
         const uint64_t x = order[e].second;
         ++row_entry[order[e].first.first + 1];
         for (uint64_t c = coord_begin[x]; c < coord_begin[x + 1]; ++c) {
-            if (c > coord_begin[x] && coords[c] < coords[c - 1]) return afail(MGX_ERR_INVALID, "mgx_annotation_set_coordinates: coordinates must be ascending");
+            if (c > coord_begin[x] && coords[c] < coords[c - 1]) return afail(MGX_ERR_INVALID, "%s", MSG_COORD_ORDER);
             flat.push_back(coords[c]);
         }
         coord_off[e + 1] = flat.size();
@@ -456,6 +484,84 @@ int mgx_annotation_set_coordinates(mgx_annotation *a, uint32_t n_labels, const u
     if (flat.size()) HIP_TRY_A(hipMemcpy(a->coords, flat.data(), flat.size() * 8, hipMemcpyHostToDevice));
     a->n_entries = n_pairs; a->n_coords = flat.size();
     a->bytes += row_entry.size() * 8 + coord_off.size() * 8 + flat.size() * 8;
+    return MGX_OK;
+}
+
+/* mgx_annotation_set_coordinates with rows, coord_begin and coords in device memory (col_begin: a host array), the row-major
+ * form built by kernels: the (row, label) order from the key sort of mgx_annotation_create_sparse with the entry index as its
+ * value, row_entry from a per-row count and a scan, coord_off from the gathered tuple lengths and a scan, the coordinates by a
+ * copy kernel with one lane per coordinate.  One kernel looks for a row outside the matrix and for a descending tuple; the call
+ * then returns the code and message of mgx_annotation_set_coordinates.  Launches and allocations do not depend on n_labels. */
+int mgx_annotation_set_coordinates_device(mgx_annotation *a, uint32_t n_labels, const uint64_t *col_begin, const uint64_t *rows,
+                                          const uint64_t *coord_begin, const int64_t *coords) {
+    if (!a || !col_begin || n_labels != a->n_labels) return afail(MGX_ERR_INVALID, "mgx_annotation_set_coordinates_device: bad arguments");
+    const uint64_t n_pairs = col_begin[n_labels], n_rows = a->n_rows;
+    if (n_pairs && (!rows || !coord_begin)) return afail(MGX_ERR_INVALID, "mgx_annotation_set_coordinates_device: bad arguments");
+    if (mgx_device_count() <= a->device) return afail(MGX_ERR_NO_DEVICE, "no HIP device");
+    HIP_TRY_A(hipSetDevice(a->device));
+    struct Tmp {                                        // the call's scratch, freed however it ends
+        std::vector<void *> p;
+        ~Tmp() { for (void *x : p) (void)hipFree(x); }
+        hipError_t alloc(void **out, uint64_t bytes) { const hipError_t e = hipMalloc(out, bytes ? bytes : 8); if (e == hipSuccess) p.push_back(*out); return e; }
+    } tmp;
+    uint64_t n_coords = 0;
+    if (n_pairs) HIP_TRY_A(hipMemcpy(&n_coords, coord_begin + n_pairs, 8, hipMemcpyDeviceToHost));
+    if (n_coords && !coords) return afail(MGX_ERR_INVALID, "mgx_annotation_set_coordinates_device: bad arguments");
+    uint64_t *d_cb = nullptr, *d_err = nullptr, *keys = nullptr, *keys_s = nullptr, *perm = nullptr, *perm_s = nullptr;
+    void *d_tmp = nullptr;
+    const uint32_t tb = 256;
+    auto blocks = [&](uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + tb - 1) / tb); };
+    HIP_TRY_A(tmp.alloc((void **)&d_cb, ((uint64_t)n_labels + 1) * 8));
+    HIP_TRY_A(hipMemcpy(d_cb, col_begin, ((uint64_t)n_labels + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY_A(tmp.alloc((void **)&d_err, 8));
+    HIP_TRY_A(hipMemset(d_err, 0xFF, 8));
+    HIP_TRY_A(tmp.alloc((void **)&keys, n_pairs * 8));
+    HIP_TRY_A(tmp.alloc((void **)&keys_s, n_pairs * 8));
+    HIP_TRY_A(tmp.alloc((void **)&perm, n_pairs * 8));
+    HIP_TRY_A(tmp.alloc((void **)&perm_s, n_pairs * 8));
+    const uint64_t n_items = std::max(n_pairs, n_coords);
+    if (n_items) k_ct_check<<<blocks(n_items), tb>>>(rows, n_pairs, n_rows, coord_begin, coords, n_coords, n_items, d_err);
+    if (n_pairs) {
+        k_ct_keys<<<blocks(n_pairs), tb>>>(d_cb, n_labels, rows, n_pairs, n_rows, keys, perm);
+        int end_bit = 24;
+        while (end_bit < 64 && (n_rows >> (end_bit - 24))) ++end_bit;
+        size_t sort_bytes = 0;
+        HIP_TRY_A(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, keys_s, perm, perm_s, n_pairs, 0, end_bit));
+        HIP_TRY_A(tmp.alloc(&d_tmp, sort_bytes));
+        HIP_TRY_A(hipcub::DeviceRadixSort::SortPairs(d_tmp, sort_bytes, keys, keys_s, perm, perm_s, n_pairs, 0, end_bit));
+    }
+    uint64_t err = CT_NO_ERROR;
+    HIP_TRY_A(hipMemcpy(&err, d_err, 8, hipMemcpyDeviceToHost));
+    if (err != CT_NO_ERROR) return afail(MGX_ERR_INVALID, "%s", (err >> 62) == CT_ROW ? MSG_COORD_ROW : MSG_COORD_ORDER);
+    // the new tables: the annotation's only once they are complete
+    uint64_t *row_entry = nullptr, *coord_off = nullptr;
+    int64_t *flat = nullptr;
+    void *d_scan = nullptr;
+    auto drop = [&]() { (void)hipFree(row_entry); (void)hipFree(coord_off); (void)hipFree(flat); };
+#define HIP_TRY_T(e) do { hipError_t r_ = (e); if (r_ != hipSuccess) { drop(); return afail(MGX_ERR_NO_DEVICE, "%s: %s", #e, hipGetErrorString(r_)); } } while (0)
+    HIP_TRY_T(hipMalloc(&row_entry, (n_rows + 1) * 8));
+    HIP_TRY_T(hipMalloc(&coord_off, (n_pairs + 1) * 8));
+    HIP_TRY_T(hipMemset(row_entry, 0, (n_rows + 1) * 8));
+    if (n_pairs) k_ct_row_count<<<blocks(n_pairs), tb>>>(keys_s, n_pairs, n_rows, row_entry);
+    k_ct_tuple_len<<<blocks(n_pairs + 1), tb>>>(perm_s, coord_begin, n_pairs, n_coords, coord_off);
+    size_t scan_bytes = 0, scan_bytes2 = 0;
+    HIP_TRY_T(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, row_entry, row_entry, n_rows + 1));
+    HIP_TRY_T(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes2, coord_off, coord_off, n_pairs + 1));
+    HIP_TRY_T(tmp.alloc(&d_scan, std::max(scan_bytes, scan_bytes2)));
+    HIP_TRY_T(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, row_entry, row_entry, n_rows + 1));
+    HIP_TRY_T(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes2, coord_off, coord_off, n_pairs + 1));
+    uint64_t total = 0;
+    HIP_TRY_T(hipMemcpy(&total, coord_off + n_pairs, 8, hipMemcpyDeviceToHost));
+    HIP_TRY_T(hipMalloc(&flat, std::max<uint64_t>(1, total) * 8));
+    if (total) k_ct_copy<<<blocks(total), tb>>>(coord_off, perm_s, coord_begin, coords, n_pairs, n_coords, total, flat);
+    HIP_TRY_T(hipGetLastError());
+    HIP_TRY_T(hipDeviceSynchronize());
+#undef HIP_TRY_T
+    if (a->row_entry) a->bytes -= (a->n_rows + 1) * 8 + (a->n_entries + 1) * 8 + a->n_coords * 8;
+    (void)hipFree(a->row_entry); (void)hipFree(a->coord_off); (void)hipFree(a->coords);
+    a->row_entry = row_entry; a->coord_off = coord_off; a->coords = flat;
+    a->n_entries = n_pairs; a->n_coords = total;
+    a->bytes += (n_rows + 1) * 8 + (n_pairs + 1) * 8 + total * 8;
     return MGX_OK;
 }
 int mgx_annotation_has_coordinates(const mgx_annotation *a) { return a && a->row_entry != nullptr; }
