@@ -120,7 +120,8 @@ typedef struct mgx_config {
                                         * chaining runs on the host inside mgx_fetch_results / mgx_align_batch; results left
                                         * on the device (mgx_device_results) are the un-chained ones: decode them and call
                                         * mgx_chain_alignments.  Not with an annotation. */
-    uint8_t global_xdrop;              /* :51 (must be 1) */
+    uint8_t global_xdrop;              /* :51; 0 = per-branch x-drop: label-aware aligners only (mgx_labeled_aligner_create), a plain
+                                          aligner gives MGX_ERR_UNSUPPORTED as the reference's DBGAligner throws */
     uint8_t allow_left_trim;           /* :52 */
     uint8_t no_backtrack;              /* :53 (must be 0) */
     uint8_t seed_complexity_filter;    /* :54 */
@@ -257,7 +258,8 @@ typedef struct mgx_stats {
                                    Both counters count label-aware reads too (k_lane_exact_labeled: one label all along) */
 } mgx_stats;
 enum { MGX_KERNEL_GRP8 = 1, MGX_KERNEL_GRP8_PRIM = 2, MGX_KERNEL_GRP8_ALT = 4, MGX_KERNEL_EXT64 = 8, MGX_KERNEL_LANE = 16,
-       MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64 /* the label-aware builds of the 64-lane and the 8-lane kernel */ };
+       MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64, /* the label-aware builds of the 64-lane and the 8-lane kernel */
+       MGX_KERNEL_LAB64_BX = 128, MGX_KERNEL_GRP8_LAB_BX = 256 /* ... and their builds with per-branch x-drop (global_xdrop = 0) */ };
 
 int mgx_device_count(void);                 /* number of visible HIP devices (0 without a GPU) */
 const char *mgx_last_error(void);
@@ -410,7 +412,9 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *                        label-aware aligners: 2 = every batch on the 64-lane labeled kernel
  *   groups_per_wave=n    8-lane kernel: n = 1 .. 8 groups of a wavefront take reads, 0 = all (default: from the batch size)
  *   multi_pass=0|1       one extension per read and launch (default: automatic from the seeds per read)
- *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic)
+ *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic).  1 means "where the configuration
+ *                        allows it": an aligner with global_xdrop = 0 (per-branch x-drop) never runs it, nor its exact exit below —
+ *                        the lane kernels encode the global rule (mgx_stats: n_lane_reads and both exact counters stay 0)
  *   exact=0|1|2          the lane kernel's exact exit: reads whose result is known when seeding ends are finished in closed form,
  *                        without DP.  1: reads whose first seed spans the query; 2: also reads whose first seed starts at the query's
  *                        first character and whose every k-mer is a node (perfect reads that cross a fork or a merge).  Default:
@@ -585,7 +589,14 @@ int mgx_chain_seeds(const mgx_config *config, int device, const mgx_chain_anchor
  * (aligner_labeled.cpp:110,143-146) and a release build reads through a null pointer.  The library answers such a look-up
  * with the labels of the node's representative — what a fetch would have found; the oracle does the same and counts them
  * (orc_unfetched_label_lookups: 0 on the reference's own label tests, which is what pins this path; reads that do need
- * such a look-up agree between library and oracle but have no reference behaviour to agree with). */
+ * such a look-up agree between library and oracle but have no reference behaviour to agree with).
+ * config->global_xdrop = 0 is accepted here (and only here): per-branch x-drop (aligner_extender_methods.cpp:429-441,511-536,
+ * 577-603,635-663) — every child of a fork gets an x-drop cut-off of its own, max_nodes_per_seq_char counts a branch's depth and
+ * ends that branch only, and a cell keeps an extension going only within rel_score_cutoff of the best score reached at its query
+ * position (scores_reached_).  Such an aligner extends on builds of the two label-aware kernels with that rule compiled in
+ * (MGX_KERNEL_LAB64_BX / MGX_KERNEL_GRP8_LAB_BX) and never on the lane-per-read kernels; the table of an extension is then no longer
+ * bounded by max_nodes_per_seq_char x query length, so a read may outgrow max_columns and is re-run by the capacity retry.  The
+ * reference sets this together with seed chaining for annotations with coordinates; chaining itself stays refused (above). */
 int mgx_labeled_aligner_create(const mgx_graph *graph, const mgx_config *config, const mgx_limits *limits,
                                const mgx_annotation *annotation, mgx_aligner **out);
 /* mgx_format_tsv for label-aware results: every alignment's fields are followed by its labels' names joined by ';'

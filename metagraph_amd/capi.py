@@ -118,6 +118,7 @@ class Stats(C.Structure):
 
 
 KERNEL_GRP8, KERNEL_GRP8_PRIM, KERNEL_GRP8_ALT, KERNEL_EXT64, KERNEL_LANE, KERNEL_LAB64, KERNEL_GRP8_LAB = 1, 2, 4, 8, 16, 32, 64
+KERNEL_LAB64_BX, KERNEL_GRP8_LAB_BX = 128, 256      # the label-aware builds with per-branch x-drop (global_xdrop = 0)
 
 
 def results_to_py(res):

@@ -81,6 +81,21 @@ namespace mgx {
 
 constexpr bool kWithPrimary = MGX_WITH_PRIMARY != 0;
 constexpr bool kWithLabels = MGX_WITH_LABELS != 0;
+// Per-branch x-drop (DBGAlignerConfig::global_xdrop == false, aligner_extender_methods.cpp:429-441,511-536,577-603,635-663): every
+// child of a fork gets a cut-off of its own, the node limit counts a branch's depth and stops that branch only, and a cell keeps
+// an extension going only if it comes within rel_score_cutoff of the best score seen at its query position (scores_reached_).
+// Compiled into label-aware builds made with -DMGX_BRANCH_XDROP=1 (their own kernel units: the others keep their code) and into
+// the host model; DevConfig::branch_xdrop switches it on.
+#ifndef MGX_BRANCH_XDROP
+#if MGX_WAVE_EMU && MGX_WITH_LABELS
+#define MGX_BRANCH_XDROP 1
+#else
+#define MGX_BRANCH_XDROP 0
+#endif
+#endif
+#if MGX_BRANCH_XDROP && !MGX_WITH_LABELS
+#error "MGX_BRANCH_XDROP needs MGX_WITH_LABELS (only label-aware aligners accept global_xdrop = 0)"
+#endif
 
 #if defined(MGX_PARAMS_IN_LDS) && MGX_PARAMS_IN_LDS
 __shared__ AlignParams g_params;
@@ -296,6 +311,9 @@ struct ExtenderState {           // one per strand (Extender object in dbg_align
     ConvChecker conv;
     uint32_t table_cap;          // capacity of the reference's std::vector<DPTColumn>
     int32_t rc_view;             // 1 while this extender runs on the RCDBG view
+#if MGX_BRANCH_XDROP
+    uint32_t xc_cap, sr_cap;     // capacities of the reference's xdrop_cutoffs_ and scores_reached_ (members of the extender, like table)
+#endif
 };
 
 struct ExtendResult { int32_t n_tips; int32_t min_cell_score; int32_t table_size; };
@@ -330,16 +348,19 @@ struct XState {
     uint64_t table_size_bytes;
     int32_t start, window_size, qlen, partial_sum_offset, seed_off, seed_seq_len, psum_lin, force_fixed;
     int32_t f_idx, f_offset, f_trim, f_size, f_max_pos, f_max_val, f_org, f_n_out;
-    uint32_t f_node, pad_;
+    uint32_t f_node;
+    uint32_t f_xi;                        // per-branch x-drop: the chain column's entry of the cut-off vector (xdrop_cutoff is its value)
     // copies of what the chain step reads every column (the seed lives in its caller's private frame and the
     // parameter block behind a generic pointer: both would be FLAT loads there)
     const uint32_t *seed_nodes;
     const uint8_t *seed_seq;
     double rel_cutoff, max_nodes_per_char, max_ram;
     int32_t go, ge, xdrop, k, Lq, max_columns, seq_lds, rc;
-    int32_t n_valid, n_for, n_count, pad3_;   // children of column n_for enumerated ahead of time into Wave::out_* (chain path)
+    int32_t n_valid, n_for, n_count;      // children of column n_for enumerated ahead of time into Wave::out_* (chain path)
+    int32_t n_xcut;                       // per-branch x-drop: xdrop_cutoffs_.size()
     uint32_t alias_ok, cell_words;        // alias_ok: a node's first chain column enters the convergence table as an alias
-    int32_t seed_n_nodes, sn_base, sc_base, pad4_;   // seed replay: first entry of the register-cached node / character run
+    int32_t seed_n_nodes, sn_base, sc_base;   // seed replay: first entry of the register-cached node / character run
+    int32_t sr_size;                      // per-branch x-drop: scores_reached_.size()
 };
 // what the backtracking keeps between its steps (bt_begin / bt_step); overlays XState, which is dead by then
 struct BtState {
@@ -461,6 +482,13 @@ struct Wave {
     uint32_t out_lab[5];         // label sets of the children in out_nodes
     uint32_t *agg;               // the per-label aggregator's queues (label_driver.hpp)
 #endif
+#if MGX_BRANCH_XDROP
+    // per-branch x-drop (arena): the values of xdrop_cutoffs_ (at most one entry per column), every column's entry
+    // (DPTColumn::xdrop_cutoff_i) and scores_reached_ (one entry per window position + 1)
+    int32_t *xcut;               // [max_columns]
+    uint32_t *col_xi;            // [max_columns]
+    int32_t *sr;                 // [Lmax + 16]
+#endif
 };
 
 MGX_DEV Block wave_blk_cache(const Wave &w) {
@@ -506,7 +534,7 @@ MGX_HD uint64_t lab_agg_words(const DevLimits &lim) { return 16 + (uint64_t)lim.
 #ifndef MGX_ARENA_REDZONE
 #define MGX_ARENA_REDZONE 0
 #endif
-constexpr uint64_t ARENA_REDZONES = 21;                 // take_rz() calls of carve() (16 + 5 of the label part)
+constexpr uint64_t ARENA_REDZONES = 23;                 // take_rz() calls of carve() (16 + 5 of the label part + 2 of per-branch x-drop)
 #if MGX_ARENA_REDZONE
 #include <sanitizer/asan_interface.h>
 #endif
@@ -543,7 +571,8 @@ MGX_HD uint64_t arena_bytes(const DevLimits &lim) {
         b += align8((uint64_t)lim.n_aln * sizeof(DevAln));
     if (lim.lab_words)                                  // label-aware alignment: set arena, column / seed handles, aggregator queues
         b += align8((uint64_t)lim.lab_words * 4) + align8((uint64_t)lim.max_columns * 4) + 2 * align8((uint64_t)lim.max_seeds * 4)
-             + align8(lab_agg_words(lim) * 4);
+             + align8(lab_agg_words(lim) * 4)
+             + 2 * align8((uint64_t)lim.max_columns * 4);      // per-branch x-drop: cut-off vector, the columns' entries (the slice's tail)
     b += ARENA_REDZONES * MGX_ARENA_REDZONE;
     return (b + 63) & ~63ull;          // slices keep the 32-byte alignment of the hash slots and the 16-byte one of the cell records
 }
@@ -612,7 +641,10 @@ MGX_DEV void carve(Wave &w, const AlignParams &P, uint8_t *base, uint8_t *lds, u
         if (cap < 16) cap = 0;
         w.st_cap = (int32_t)cap;
         int32_t *hi[6];
-        for (int a = 0; a < 6; ++a) hi[a] = (int32_t *)take(full * 4);          // (6th slot kept for layout stability)
+        for (int a = 0; a < 6; ++a) hi[a] = (int32_t *)take(full * 4);          // (6th slot: scores_reached_ of per-branch x-drop builds)
+#if MGX_BRANCH_XDROP
+        w.sr = hi[5];
+#endif
         int32_t *lo[5];
         for (int a = 0; a < 5; ++a) { lo[a] = (int32_t *)lp; lp += cap * 4; lleft -= (uint32_t)(cap * 4); }
         w.st[0].S = { lo[0], hi[0] }; w.st[0].F = { lo[1], hi[1] };
@@ -665,8 +697,15 @@ MGX_DEV void carve(Wave &w, const AlignParams &P, uint8_t *base, uint8_t *lds, u
         w.col_lab = (uint32_t *)take_rz((uint64_t)lim.max_columns * 4);
         for (int s = 0; s < 2; ++s) w.seed_lab[s] = (uint32_t *)take_rz((uint64_t)lim.max_seeds * 4);
         w.agg = (uint32_t *)take_rz(lab_agg_words(lim) * 4);
+#if MGX_BRANCH_XDROP
+        w.xcut = (int32_t *)take_rz((uint64_t)lim.max_columns * 4);
+        w.col_xi = (uint32_t *)take_rz((uint64_t)lim.max_columns * 4);
+#endif
     } else {
         w.lab = nullptr; w.col_lab = nullptr; w.seed_lab[0] = w.seed_lab[1] = nullptr; w.agg = nullptr;
+#if MGX_BRANCH_XDROP
+        w.xcut = nullptr; w.col_xi = nullptr;
+#endif
     }
 #endif
 }
@@ -2722,6 +2761,12 @@ MGX_DEV void fast_load(Wave &w, const ColMeta &c, int32_t idx, LV<int32_t> *S, L
     x.f_idx = idx; x.f_node = c.node; x.f_offset = c.offset; x.f_trim = c.trim; x.f_size = c.size; x.f_max_pos = c.max_pos;
     const int32_t org = c.trim & ~3;
     x.f_org = org;
+#if MGX_BRANCH_XDROP
+    if (MGX_PARAMS_OF(w).cfg.branch_xdrop) {                  // the chain runs on this column's entry of the cut-off vector
+        x.f_xi = uni(gld(w.col_xi + idx));
+        x.xdrop_cutoff = uni(gld(w.xcut + x.f_xi));
+    }
+#endif
     const int32_t n = c.size + 5;
     const int sb = (w.st[0].col == idx) ? 0 : (w.st[1].col == idx) ? 1 : -1;
     if (sb >= 0) {
@@ -2787,6 +2832,36 @@ namespace mgx {
 #include "label_sets.hpp"
 #endif
 
+#if MGX_BRANCH_XDROP
+// scores_reached_.resize(new_size, ninf) before a column's scan (:637-641): what lay beyond a smaller new size is lost.  Returns the
+// growth of the vector's capacity (std::vector::resize grows to size + max(size, added))
+MGX_DEV uint32_t reach_resize(Wave &w, ExtenderState &E, const int32_t new_size) {
+    XState &x = w.x;
+    const int32_t old = x.sr_size;
+    uint32_t grown = 0;
+    if (new_size > old) {
+        if ((uint32_t)new_size > E.sr_cap) {
+            const uint32_t nc = (uint32_t)old + (uint32_t)imax(old, new_size - old);
+            grown = nc - E.sr_cap;
+            E.sr_cap = nc;
+        }
+        for (int32_t base = old; base < new_size; base += WAVE) {
+            FOR_LANES(l) { const int32_t j = base + l; if (j < new_size) gst(w.sr + j, NINF); }
+        }
+        wave_sync();
+    }
+    x.sr_size = new_size;
+    return grown;
+}
+// one cell of the scan (:652-655): scores_reached_[pos] = max(old, s); does s come within rel_score_cutoff of it?  (an int against a
+// double, as in the reference: false for a negative s at rel_score_cutoff < 1)
+MGX_DEV bool reach_cell(int32_t *sr, const int32_t pos, const int32_t s, const double rel_cutoff) {
+    const int32_t r = imax(gld(sr + pos), s);
+    gst(sr + pos, r);
+    return (double)s >= (double)r * rel_cutoff;
+}
+#endif
+
 // ---- general path: one popped column `i` with all its children (staging buffers, frontier arrays) ----
 // returns 0, or 1 = the extension is over (capacity error; w.status says which)
 MGX_DEV int general_step(Wave &w, ExtenderState &E, const int32_t i, const bool children_ready) {
@@ -2809,12 +2884,20 @@ MGX_DEV int general_step(Wave &w, ExtenderState &E, const int32_t i, const bool 
     const Staging par = w.st[pb];
     const int32_t cap = uni(w.st_cap);
     const int32_t next_offset = col.offset + 1;
+#if MGX_BRANCH_XDROP
+    const bool bx = cfg.branch_xdrop != 0;
+    const uint32_t prev_xi = bx ? uni(gld(w.col_xi + i)) : 0u;
+    const int32_t prev_xdrop_cutoff = bx ? uni(gld(w.xcut + prev_xi)) : x.xdrop_cutoff;     // the column's own entry, or the one shared cutoff
+#else
+    constexpr bool bx = false;
     const int32_t prev_xdrop_cutoff = x.xdrop_cutoff;       // global_xdrop: one shared cutoff
+#endif
     const bool in_seed = (next_offset - seed_off) >= 0 && (next_offset - seed_off) < seed_seq_len;
     // early cut-offs when off the optimal path (:521-547)
     if (!children_ready && uni(st_S(par, cap, col.size, col.max_pos - col.trim)) < x.best_score) {
-        double node_counter = (double)x.tsize;
-        if (node_counter / (double)window_size >= max_nodes_per_char) { x.qn = 0; x.nn = 0; return 0; }
+        // (per-branch x-drop counts the branch's depth and ends this branch only, :521-536)
+        double node_counter = bx ? (double)(next_offset - seed_offset) : (double)x.tsize;
+        if (node_counter / (double)window_size >= max_nodes_per_char) { if (bx) return 0; x.qn = 0; x.nn = 0; return 0; }
         if ((double)x.table_size_bytes / 1000000.0 > max_ram) { x.qn = 0; x.nn = 0; return 0; }
     }
     // band within the x-drop cutoff (:549-560)
@@ -2863,6 +2946,19 @@ MGX_DEV int general_step(Wave &w, ExtenderState &E, const int32_t i, const bool 
         int32_t size0 = end - begin;
         uint32_t need = rec_words((uint32_t)(window_size + 1 - begin + 8));     // the column may grow to the window end
         if ((uint64_t)x.cell_top + need > cell_words) { w.status = ST_CAPACITY; return 1; }
+#if MGX_BRANCH_XDROP
+        // (:578-586) every child of a fork gets a cut-off of its own, starting from its parent's; an only child shares its parent's
+        const bool forked = bx && n_out > 1;
+        uint32_t cur_xi = prev_xi, xcut_grown = 0;
+        if (forked) {
+            if (x.n_xcut >= max_columns) { w.status = ST_CAPACITY; return 1; }
+            if ((uint32_t)x.n_xcut == E.xc_cap) { xcut_grown = E.xc_cap; E.xc_cap *= 2; }        // emplace_back doubles
+            cur_xi = (uint32_t)x.n_xcut++;
+        }
+        // x.xdrop_cutoff is the cut-off of the column being computed: the value of its entry, written back when the column stays
+        // (an only child's entry is its parent's, unchanged since the pop; a forked child's starts from it)
+        if (bx) x.xdrop_cutoff = prev_xdrop_cutoff;
+#endif
         uint32_t table_cap_before = E.table_cap;
         if ((uint32_t)x.tsize == E.table_cap) E.table_cap = imax<uint32_t>(1u, 2 * E.table_cap);
         ++w.n_columns;
@@ -2881,6 +2977,13 @@ MGX_DEV int general_step(Wave &w, ExtenderState &E, const int32_t i, const bool 
             uni((int32_t)fma_f64((double)x.best_score, rel_cutoff, (double)x.partial_sum_offset));
         int32_t best_s = INT32_MIN, best_d = INT32_MAX, best_j = 0;
         int32_t min_cell_score = x.min_cell_score;
+#if MGX_BRANCH_XDROP
+        uint32_t reach_grown = 0;
+        if (bx) {
+            if ((uint32_t)(size + begin + 1) > lim.Lmax + 16) { w.status = ST_CAPACITY; return 1; }      // cannot happen: size + trim <= window + 1
+            reach_grown = reach_resize(w, E, size + begin + 1);
+        }
+#endif
         for (int32_t base = 0; base < size; base += WAVE) {
             LV<int32_t> sv, mn, dd;
             LV<bool> ext;
@@ -2890,6 +2993,9 @@ MGX_DEV int general_step(Wave &w, ExtenderState &E, const int32_t i, const bool 
                 sv[l] = v;
                 mn[l] = (j < size && v != NINF) ? v : INT32_MAX;
                 ext[l] = j < size && v + (psum_lin ? (qlen - (start + begin + j)) * psum_lin : psum[start + begin + j]) >= extension_cutoff;
+#if MGX_BRANCH_XDROP
+                if (bx && j < size) { const bool near = reach_cell(w.sr, begin + j, v, rel_cutoff); ext[l] = ext[l] && near; }
+#endif
             }
             min_cell_score = imin(min_cell_score, wave_min(mn));
             if (wave_ballot(ext)) has_extension = true;
@@ -2907,11 +3013,21 @@ MGX_DEV int general_step(Wave &w, ExtenderState &E, const int32_t i, const bool 
         const int32_t max_val = best_s;
         if ((!in_seed && max_val < x.xdrop_cutoff) || (!in_seed && !has_extension)) {
             // pop(table.size() - 1): the vector keeps its (possibly grown) capacity
+#if MGX_BRANCH_XDROP
+            if (forked) --x.n_xcut;                         // xdrop_cutoffs_.pop_back(): so does this one
+#endif
             continue;
         }
         uint32_t table_sizediff = E.table_cap - table_cap_before;
         x.table_size_bytes += (uint64_t)136 * table_sizediff + (uint64_t)cur_cap3 * 4;
         if ((int32_t)((uint32_t)max_val - (uint32_t)x.xdrop_cutoff) > xdrop) x.xdrop_cutoff = max_val - xdrop;
+#if MGX_BRANCH_XDROP
+        if (bx) {
+            x.table_size_bytes += (uint64_t)4 * reach_grown + (uint64_t)16 * xcut_grown;     // sizeof(score_t), sizeof(std::pair<size_t, score_t>)
+            gst(w.xcut + cur_xi, x.xdrop_cutoff);
+            gst(w.col_xi + x.tsize, cur_xi);
+        }
+#endif
         x.best_score = imax(x.best_score, max_val);
         // commit the column: metadata + cells go to the arena (nothing waits on them)
         const int32_t cur_wc = flush_column(w, w.st[cb], x.cell_top, size, uni(cfg.gap_ext), &w.st[pb], col.size, begin - col.trim,
@@ -2970,9 +3086,15 @@ MGX_DEV int chain_step(Wave &w, ExtenderState &E, LV<int32_t> *pS, LV<int32_t> *
     uint64_t tch = tx1;
 #endif
     // early cut-offs when off the optimal path (:521-547)
+#if MGX_BRANCH_XDROP
+    const bool bx = MGX_PARAMS_OF(w).cfg.branch_xdrop != 0;
+#else
+    constexpr bool bx = false;
+#endif
     if (x.f_max_val < x.best_score) {
-        double node_counter = (double)x.tsize;
-        if (node_counter / (double)window_size >= x.max_nodes_per_char) return FR_STOP;
+        // (per-branch x-drop counts the branch's depth and ends this branch only, :521-536)
+        double node_counter = bx ? (double)(x.f_offset + 1 - (x.seed_off - 1)) : (double)x.tsize;
+        if (node_counter / (double)window_size >= x.max_nodes_per_char) return bx ? FR_END : FR_STOP;
         if ((double)x.table_size_bytes / 1000000.0 > x.max_ram) return FR_STOP;
     }
     int32_t p_org = x.f_org;
@@ -3247,6 +3369,10 @@ MGX_DEV int chain_step(Wave &w, ExtenderState &E, LV<int32_t> *pS, LV<int32_t> *
     const int32_t extension_cutoff = (int32_t)fma_f64((double)x.best_score, x.rel_cutoff, (double)x.partial_sum_offset);
     LV<int32_t> lmax, lmin;
     LV<bool> lext;
+#if MGX_BRANCH_XDROP
+    uint32_t reach_grown = 0;
+    if (bx) reach_grown = reach_resize(w, E, size + begin + 1);      // (size + begin <= window + 1 <= Lmax + 1: inside the array)
+#endif
     FOR_LANES(l) {
         int32_t mx = INT32_MIN, mn = INT32_MAX;
         bool ext = false;
@@ -3256,7 +3382,13 @@ MGX_DEV int chain_step(Wave &w, ExtenderState &E, LV<int32_t> *pS, LV<int32_t> *
                 const int32_t v = cS[s][l];
                 mx = imax(mx, v);
                 if (v != NINF) mn = imin(mn, v);
+#if MGX_BRANCH_XDROP
+                bool e = v + (psum_lin ? (qlen - (start + a)) * psum_lin : psum[start + a]) >= extension_cutoff;
+                if (bx) { const bool near = reach_cell(w.sr, a, v, x.rel_cutoff); e = e && near; }
+                ext |= e;
+#else
                 ext |= v + (psum_lin ? (qlen - (start + a)) * psum_lin : psum[start + a]) >= extension_cutoff;
+#endif
             }
         }
         lmax[l] = mx; lmin[l] = mn; lext[l] = ext;
@@ -3282,6 +3414,13 @@ MGX_DEV int chain_step(Wave &w, ExtenderState &E, LV<int32_t> *pS, LV<int32_t> *
     const uint32_t cur_cap3 = 3 * ref_capacity((uint32_t)size0, (uint32_t)pushes);
     x.table_size_bytes += (uint64_t)136 * (E.table_cap - table_cap_before) + (uint64_t)cur_cap3 * 4;
     if ((int32_t)((uint32_t)max_val - (uint32_t)xdrop_cutoff) > x.xdrop) x.xdrop_cutoff = max_val - x.xdrop;
+#if MGX_BRANCH_XDROP
+    if (bx) {                                  // an only child: its parent's entry of the cut-off vector, no new one
+        x.table_size_bytes += (uint64_t)4 * reach_grown;
+        gst(w.xcut + x.f_xi, x.xdrop_cutoff);
+        gst(w.col_xi + x.tsize, x.f_xi);
+    }
+#endif
     x.best_score = imax(x.best_score, max_val);
     CH_T(3)
     // --- everything that LOADS comes first (a wait on a load also waits for every store issued before it) ---
@@ -3701,6 +3840,18 @@ MGX_DEV bool extend_begin(Wave &w, const int es, const SeedRef &seed, bool force
         x.tsize = 1;
         x.table_size_bytes = (uint64_t)136 * E.table_cap + (uint64_t)root_cap3 * 4;
     }
+#if MGX_BRANCH_XDROP
+    if (cfg.branch_xdrop) {
+        // xdrop_cutoffs_.assign(1, ...), scores_reached_.assign(1, 0) (:431-441): the root's entry; both vectors keep their capacity
+        gst(w.xcut, x.xdrop_cutoff);
+        gst(w.col_xi, 0u);
+        gst(w.sr, 0);
+        x.n_xcut = 1; x.sr_size = 1; x.f_xi = 0;
+        if (E.xc_cap < 1) E.xc_cap = 1;
+        if (E.sr_cap < 1) E.sr_cap = 1;
+        wave_sync();
+    }
+#endif
     x.min_cell_score = 0;
     x.best_score = 0;
     x.qn = 0; x.nn = 0; x.n_tips = 0;
@@ -4604,6 +4755,9 @@ MGX_DEV void resume_save(Wave &w, uint8_t *rec) {
             h[0] = w.resume_phase; h[1] = w.resume_i; h[2] = w.have_best;
             h[3] = (int32_t)w.ext[0].table_cap; h[4] = (int32_t)w.ext[1].table_cap;
             h[5] = (int32_t)w.n_extensions; h[6] = (int32_t)w.n_columns; h[7] = (int32_t)w.n_fast_columns;
+#if MGX_BRANCH_XDROP
+            h[8] = (int32_t)w.ext[0].xc_cap; h[9] = (int32_t)w.ext[1].xc_cap; h[10] = (int32_t)w.ext[0].sr_cap; h[11] = (int32_t)w.ext[1].sr_cap;
+#endif
         }
     }
     uint8_t *al = rec + 64;
@@ -4635,6 +4789,10 @@ MGX_DEV void resume_load(Wave &w, const uint8_t *rec) {
     w.resume_phase = uni(h[0]); w.resume_i = uni(h[1]); w.have_best = uni(h[2]);
     w.ext[0].table_cap = (uint32_t)uni(h[3]); w.ext[1].table_cap = (uint32_t)uni(h[4]);
     w.n_extensions = (uint32_t)uni(h[5]); w.n_columns = (uint32_t)uni(h[6]); w.n_fast_columns = (uint32_t)uni(h[7]);
+#if MGX_BRANCH_XDROP
+    w.ext[0].xc_cap = (uint32_t)uni(h[8]); w.ext[1].xc_cap = (uint32_t)uni(h[9]);
+    w.ext[0].sr_cap = (uint32_t)uni(h[10]); w.ext[1].sr_cap = (uint32_t)uni(h[11]);
+#endif
     const uint8_t *al = rec + 64;
     for (int s = 0; s < 2; ++s) {
         const int32_t n = w.n_seeds[s];
@@ -4923,6 +5081,9 @@ MGX_DEV void align_read(Wave &w, const AlignParams &P, uint64_t read, uint32_t s
             w.ext[s].psum = w.psum[s];
             w.ext[s].psum_lin = (PHASE & PH_EXTEND) ? w.psum_lin[s] : 0;
             w.ext[s].table_cap = 0;
+#if MGX_BRANCH_XDROP
+            w.ext[s].xc_cap = 0; w.ext[s].sr_cap = 0;
+#endif
             w.ext[s].rc_view = 0;
             w.ext[s].conv.n_entries = 0; w.ext[s].conv.n_recs = 0; w.ext[s].conv.pool_top = 0;
             w.ext[s].conv.cap = conv_cap0(P.lim.hash_size); w.ext[s].conv.base = 0; w.ext[s].conv.start = 0;
@@ -5504,6 +5665,9 @@ MGX_DEV bool flat_read_begin(Wave &w, const AlignParams &P, uint64_t read, uint3
         w.ext[s].psum = w.psum[s];
         w.ext[s].psum_lin = w.psum_lin[s];
         w.ext[s].table_cap = 0;
+#if MGX_BRANCH_XDROP
+        w.ext[s].xc_cap = 0; w.ext[s].sr_cap = 0;
+#endif
         w.ext[s].rc_view = 0;
         w.ext[s].conv.n_entries = 0; w.ext[s].conv.n_recs = 0; w.ext[s].conv.pool_top = 0;
         w.ext[s].conv.cap = conv_cap0(P.lim.hash_size); w.ext[s].conv.base = 0; w.ext[s].conv.start = 0;

@@ -28,6 +28,8 @@ struct DevConfig {
     uint32_t canonical;      // 1: the graph is a CANONICAL-mode DBGSuccinct (both strands stored): dbg_aligner.cpp:225,644-655;
                              // 2: a PRIMARY-mode one seen through the CanonicalDBG wrapper (canon_graph.hpp), same driver flow;
                              // 3: the same with the wrapper's look-ups read from the graph's reverse-complement tables
+    uint32_t branch_xdrop;   // global_xdrop == false: per-branch x-drop (label-aware aligners; the kernel builds with MGX_BRANCH_XDROP).
+                             // (In what was the struct's tail padding: the parameter block keeps its size and layout.)
 };
 
 struct DevLimits {

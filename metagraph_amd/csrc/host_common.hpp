@@ -45,7 +45,12 @@ inline int prepare_config(const mgx_config &in, uint64_t k, mgx_config *out, Dev
     if (!check_config_scores(c)) { *err = "Error: sum of min_cell_score and lowest penalty too low."; return MGX_ERR_CONFIG; }
     if (c.chain_alignments) { *err = "seed chaining (chain_alignments) is not implemented"; return MGX_ERR_UNSUPPORTED; }
     if (c.post_chain_alignments && labeled) { *err = "post_chain_alignments with an annotation is not implemented"; return MGX_ERR_UNSUPPORTED; }
-    if (!c.global_xdrop) { *err = "per-branch xdrop (labeled+coordinates mode) is not implemented"; return MGX_ERR_UNSUPPORTED; }
+    // per-branch x-drop: label-aware aligners only (the reference's plain DBGAligner refuses global_xdrop = false itself, so nothing
+    // could check a plain aligner's results)
+    if (!c.global_xdrop && !labeled) {
+        *err = "global_xdrop = 0 (per-branch x-drop) is for label-aware aligners only: the reference's plain aligner refuses it as well";
+        return MGX_ERR_UNSUPPORTED;
+    }
     if (c.no_backtrack) { *err = "no_backtrack is not implemented"; return MGX_ERR_UNSUPPORTED; }
     if (c.num_alternative_paths < 1 || c.num_alternative_paths > MGX_MAX_ALTERNATIVE_PATHS) {
         *err = "num_alternative_paths must be in 1.." + std::to_string(MGX_MAX_ALTERNATIVE_PATHS) + " on the device";
@@ -68,6 +73,7 @@ inline int prepare_config(const mgx_config &in, uint64_t k, mgx_config *out, Dev
     // on the device "every" is post_chain_capacity() — a query with more gets MGX_ERR_CAPACITY, never a dropped alignment
     d->post_chain = c.post_chain_alignments ? 1u : 0u;
     d->agg_cap = c.post_chain_alignments ? post_chain_capacity(c.num_alternative_paths) : d->num_alt;
+    d->branch_xdrop = c.global_xdrop ? 0u : 1u;
     d->canonical = 0;                       // set from the graph's mode by the caller (with fwd_and_rc, dbg_aligner.cpp:225-226)
     return MGX_OK;
 }
@@ -106,7 +112,10 @@ inline int derive_limits(const mgx_config &cfg, const mgx_limits *u, uint32_t Lm
         // 98 % of the columns are chain columns that own nothing here, and the arena slices are what limits the number of
         // resident groups at 10 M reads — a quarter of that, still 24 cells x 3 per possible column.  A read that runs out gets
         // MGX_ERR_CAPACITY and the adapter's retry doubles the budget.
-        uint64_t band = cfg.xdrop < 1000 ? std::min<uint64_t>(l.Lmax + 8, 24) : (l.Lmax + 8);
+        // Per-branch x-drop (global_xdrop = 0) budgets the whole window, as a configuration without an x-drop does: a branch
+        // that falls behind keeps the cut-off it had at its fork, so its columns keep cells the one shared cut-off would have
+        // dropped, and a node limit that ends one branch leaves the others in the frontier, each column with a record.
+        uint64_t band = (cfg.xdrop < 1000 && cfg.global_xdrop) ? std::min<uint64_t>(l.Lmax + 8, 24) : (l.Lmax + 8);
         cw = (uint64_t)l.max_columns * 3 * band + 3 * (l.Lmax + 16) + 4096;
     }
     l.cell_words = (uint32_t)std::min<uint64_t>(cw, 0xFFFFFF00ull);

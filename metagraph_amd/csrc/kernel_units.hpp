@@ -44,8 +44,10 @@ MGX_DECLARE_GRP8_BUILD()
 MGX_DECLARE_GRP8_BUILD(_prim)
 MGX_DECLARE_GRP8_BUILD(_alt)
 MGX_DECLARE_GRP8_BUILD(_lab)
+MGX_DECLARE_GRP8_BUILD(_labx)        // `_lab` with per-branch x-drop compiled in (-DMGX_BRANCH_XDROP=1): aligners with global_xdrop = 0
 #undef MGX_DECLARE_GRP8_BUILD
 int mgx_grp_max_alt8_lab(void);
+int mgx_grp_max_alt8_labx(void);
 
 // mgx_ext64.hip / mgx_lab64.hip: the extension half with all 64 lanes on one read, plain and label-aware.  params: AlignParams
 // (host memory); blocks = wavefronts; lds_bytes = dynamic LDS per wavefront.
@@ -56,6 +58,11 @@ int mgx_launch_lab64(const void *params, uint32_t blocks, uint32_t lds_bytes, vo
 unsigned mgx_lab64_static_lds(void);
 int mgx_lab64_waves_per_simd(void);
 int mgx_lab64_max_alt(void);
+// ... and the build of mgx_lab64.hip with per-branch x-drop compiled in (-DMGX_BRANCH_XDROP=1): aligners with global_xdrop = 0
+int mgx_launch_lab64x(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream);
+unsigned mgx_lab64x_static_lds(void);
+int mgx_lab64x_waves_per_simd(void);
+int mgx_lab64x_max_alt(void);
 
 // mgx_seed.hip: the wave-per-read seeding kernel (seed_kernel.hpp), two builds: the plain one and `_primary`
 // (-DMGX_WITH_PRIMARY=1: the CanonicalDBG branches, PRIMARY graphs).  params: AlignParams (host memory); blocks = wavefronts;

@@ -140,6 +140,7 @@ inline bool lane_enabled(const mgx_config &c, const DevConfig &d, uint32_t k, ui
     if (k > 32 || k < 2) return no("k > 32: reads are not 2-bit packed");
     if (Lmax < 1 || Lmax > (uint32_t)LANE_MAX_L_HOST) return no("reads longer than a lane takes");
     if (no_fast || c.xdrop > 30000) return no("chain path off");
+    if (d.branch_xdrop) return no("per-branch x-drop (global_xdrop = 0): the lane kernels encode the global rule");
     const char acgt[4] = { 'A', 'C', 'G', 'T' };
     const int m = c.score_matrix[(int)'A'][(int)'A'];
     if (m <= 0) return no("match score");

@@ -73,7 +73,7 @@ struct ExtBuild {
     uint64_t kernel_bit;              // MGX_KERNEL_*
     LaunchCounter counter;            // its entry of g_kernel_launches (the label-aware builds are not counted)
 };
-enum ExtBuildId { EXT_GRP8, EXT_GRP8_PRIM, EXT_GRP8_ALT, EXT_GRP8_LAB, EXT_EXT64, EXT_LAB64 };
+enum ExtBuildId { EXT_GRP8, EXT_GRP8_PRIM, EXT_GRP8_ALT, EXT_GRP8_LAB, EXT_EXT64, EXT_LAB64, EXT_GRP8_LAB_BX, EXT_LAB64_BX };
 static const ExtBuild g_ext_builds[] = {
     { mgx_launch_align_grp8, nullptr, mgx_grp_waves_per_simd8, mgx_grp_static_lds8, MGX_KERNEL_GRP8, CNT_GRP8 },
     { mgx_launch_align_grp8_prim, nullptr, mgx_grp_waves_per_simd8_prim, mgx_grp_static_lds8_prim, MGX_KERNEL_GRP8_PRIM, CNT_GRP8_PRIM },
@@ -81,12 +81,15 @@ static const ExtBuild g_ext_builds[] = {
     { mgx_launch_align_grp8_lab, nullptr, mgx_grp_waves_per_simd8_lab, mgx_grp_static_lds8_lab, MGX_KERNEL_GRP8_LAB, CNT_NONE },
     { nullptr, mgx_launch_ext64, mgx_ext64_waves_per_simd, mgx_ext64_static_lds, MGX_KERNEL_EXT64, CNT_EXT64 },
     { nullptr, mgx_launch_lab64, mgx_lab64_waves_per_simd, mgx_lab64_static_lds, MGX_KERNEL_LAB64, CNT_NONE },
+    // the label-aware builds with per-branch x-drop: what an aligner with global_xdrop = 0 launches instead of the two above
+    { mgx_launch_align_grp8_labx, nullptr, mgx_grp_waves_per_simd8_labx, mgx_grp_static_lds8_labx, MGX_KERNEL_GRP8_LAB_BX, CNT_NONE },
+    { nullptr, mgx_launch_lab64x, mgx_lab64x_waves_per_simd, mgx_lab64x_static_lds, MGX_KERNEL_LAB64_BX, CNT_NONE },
 };
 static uint32_t waves_per_cu(const ExtBuild &b) { return 4u * (uint32_t)b.waves_per_simd(); }
 // The 8-lane-group build a configuration extends on: the label-aware one; else the one with room for alternative paths
 // (either kind of graph); else, on PRIMARY graphs, the product with the CanonicalDBG branches; else the product.
-static const ExtBuild &group_build(bool labeled, bool primary, uint64_t agg_cap) {
-    return g_ext_builds[labeled ? EXT_GRP8_LAB : agg_cap > 1 ? EXT_GRP8_ALT : primary ? EXT_GRP8_PRIM : EXT_GRP8];
+static const ExtBuild &group_build(bool labeled, bool primary, uint64_t agg_cap, bool branch_xdrop) {
+    return g_ext_builds[labeled ? (branch_xdrop ? EXT_GRP8_LAB_BX : EXT_GRP8_LAB) : agg_cap > 1 ? EXT_GRP8_ALT : primary ? EXT_GRP8_PRIM : EXT_GRP8];
 }
 
 // Latency-critical scalar arrays go to LDS when they fit next to the other resident wavefronts of the CU.  The budget: a
@@ -211,8 +214,9 @@ int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limit
         // CANONICAL-mode graphs (labels looked up by base node through the CanonicalDBG wrapper, resp. by the k-mer's
         // representative: include/mgx.h), annotation without coordinates, as many alternative paths per label as the
         // labeled kernel build holds.
-        if (A->cfg.num_alternative_paths > (uint64_t)std::min(mgx_lab64_max_alt(), mgx_grp_max_alt8_lab()))
-            return fail(MGX_ERR_UNSUPPORTED, "label-aware alignment: num_alternative_paths <= %d on the device", std::min(mgx_lab64_max_alt(), mgx_grp_max_alt8_lab()));
+        const int lab_max_alt = std::min(std::min(mgx_lab64_max_alt(), mgx_grp_max_alt8_lab()), std::min(mgx_lab64x_max_alt(), mgx_grp_max_alt8_labx()));
+        if (A->cfg.num_alternative_paths > (uint64_t)lab_max_alt)
+            return fail(MGX_ERR_UNSUPPORTED, "label-aware alignment: num_alternative_paths <= %d on the device", lab_max_alt);
         int adev = 0; uint64_t arows = 0; const uint64_t *h; const uint32_t *c, *m;
         mgx_annotation_device_view(anno, &adev, &arows, &h, &c, &m);
         if (adev != g->device) return fail(MGX_ERR_INVALID, "the annotation lives on device %d, the graph on device %d", adev, g->device);
@@ -359,7 +363,7 @@ static int size_arena(mgx_aligner *A, AlignPlan &pl) {
     pl.wave_slots = (uint64_t)pl.cus * 4 * MGX_ALIGN_WAVES_PER_SIMD;
     // (post_chain_alignments keeps up to MGX_MAX_ALTERNATIVE_PATHS alignments per query: the build with room for them)
     pl.agg_cap = std::max<uint64_t>(1, A->cfg.post_chain_alignments ? (uint64_t)post_chain_capacity(A->cfg.num_alternative_paths) : A->cfg.num_alternative_paths);
-    pl.grp = &group_build(pl.labeled, A->dcfg.canonical >= 2, pl.agg_cap);
+    pl.grp = &group_build(pl.labeled, A->dcfg.canonical >= 2, pl.agg_cap, A->dcfg.branch_xdrop != 0);
     // (label-aware batches: seeding as ever, extension on the labeled builds)
     const uint64_t want_slots = std::max<uint64_t>(pl.wave_slots, (uint64_t)pl.cus * waves_per_cu(*pl.grp) * 8);
     // The arena gets what is free after the buffers this stage allocates AFTER it (result records, output stream, seed
@@ -692,7 +696,7 @@ static int launch_extension(mgx_aligner *A, AlignPlan &pl) {
     if (pl.labeled) {
         // label-aware extension: the labeled builds — 8 reads per wavefront (mgx_grp.hip, per-read program), or one read
         // per wavefront on the 64-lane kernel (mgx_lab64.hip) for batches with fewer reads than resident wavefronts
-        const ExtBuild &lab64 = g_ext_builds[EXT_LAB64];
+        const ExtBuild &lab64 = g_ext_builds[A->dcfg.branch_xdrop ? EXT_LAB64_BX : EXT_LAB64];
         const uint64_t resident64 = (uint64_t)pl.cus * waves_per_cu(lab64);
         if ((items <= resident64 && A->opt.ext64 != 0) || A->opt.ext64 == 2) {
             b = &lab64; gpw = 1;

@@ -15,7 +15,12 @@
 // 2-wave build of the alternative paths.
 // A fourth build (-DMGX_LAB_BUILD -DMGX_ALT_BUILD -DMGX_WITH_LABELS=1 -DMGX_MAX_ALT=4) carries the label-aware extender
 // (label_sets.hpp / label_driver.hpp): the batches of a mgx_labeled_aligner_create aligner, through the per-read program.
-#if defined(MGX_LAB_BUILD)
+// A fifth build is the fourth plus -DMGX_BRANCH_XDROP=1: per-branch x-drop (align_core.hpp), for label-aware aligners with
+// global_xdrop = 0.
+#if defined(MGX_LAB_BUILD) && defined(MGX_BRANCH_XDROP) && MGX_BRANCH_XDROP
+#define MGX_SUFFIX(x) MGX_CAT(x, _labx)
+#define mgx MGX_CAT(MGX_CAT(mgx_grp, MGX_GROUP), lx)
+#elif defined(MGX_LAB_BUILD)
 #define MGX_SUFFIX(x) MGX_CAT(x, _lab)
 #define mgx MGX_CAT(MGX_CAT(mgx_grp, MGX_GROUP), l)
 #elif defined(MGX_ALT_BUILD)

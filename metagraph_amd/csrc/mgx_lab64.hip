@@ -4,7 +4,17 @@
 // every other batch runs the kernels without the label hooks.  Same sources, own namespace.
 #include <hip/hip_runtime.h>
 
+// A second build (-DMGX_BRANCH_XDROP=1) carries per-branch x-drop (align_core.hpp) for aligners with global_xdrop = 0; its namespace
+// and exported names end in `x`.
+#if defined(MGX_BRANCH_XDROP) && MGX_BRANCH_XDROP
+#define mgx mgx_lab64x
+#define MGX_LAB64_SYM(x) mgx_##x##lab64x
+#define MGX_LAB64_SYM2(x) mgx_lab64x_##x
+#else
 #define mgx mgx_lab64
+#define MGX_LAB64_SYM(x) mgx_##x##lab64
+#define MGX_LAB64_SYM2(x) mgx_lab64_##x
+#endif
 #define MGX_WITH_LABELS 1
 #define MGX_WITH_PRIMARY 1
 #ifndef MGX_MAX_ALT
@@ -17,12 +27,12 @@
 
 using namespace mgx;
 
-extern "C" int mgx_launch_lab64(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream) {
+extern "C" int MGX_LAB64_SYM(launch_)(const void *params, uint32_t blocks, uint32_t lds_bytes, void *stream) {
     static_assert(sizeof(AlignParams) == MGX_ALIGN_PARAMS_BYTES, "AlignParams differs from what mgx.hip passes");
     const AlignParams &P = *static_cast<const AlignParams *>(params);
     k_align<PH_EXTEND><<<blocks, 64, lds_bytes, (hipStream_t)stream>>>(P, lds_bytes);
     return (int)hipGetLastError();
 }
-extern "C" unsigned mgx_lab64_static_lds(void) { return (unsigned)(sizeof(Wave) + sizeof(SdustScratch) + 6 * 128); }
-extern "C" int mgx_lab64_waves_per_simd(void) { return MGX_ALIGN_WAVES_PER_SIMD; }
-extern "C" int mgx_lab64_max_alt(void) { return MGX_MAX_ALT; }
+extern "C" unsigned MGX_LAB64_SYM2(static_lds)(void) { return (unsigned)(sizeof(Wave) + sizeof(SdustScratch) + 6 * 128); }
+extern "C" int MGX_LAB64_SYM2(waves_per_simd)(void) { return MGX_ALIGN_WAVES_PER_SIMD; }
+extern "C" int MGX_LAB64_SYM2(max_alt)(void) { return MGX_MAX_ALT; }

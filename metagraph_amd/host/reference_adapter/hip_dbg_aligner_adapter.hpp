@@ -89,7 +89,7 @@ inline mgx_config to_mgx_config(const DBGAlignerConfig &c) {
     m.forward_and_reverse_complement = c.forward_and_reverse_complement;
     m.chain_alignments = c.chain_alignments;
     m.post_chain_alignments = c.post_chain_alignments;
-    m.global_xdrop = c.global_xdrop;
+    m.global_xdrop = c.global_xdrop;      // (false: per-branch x-drop — the label-aware aligner takes it, the plain one answers MGX_ERR_UNSUPPORTED)
     m.allow_left_trim = c.allow_left_trim;
     m.no_backtrack = c.no_backtrack;
     m.seed_complexity_filter = c.seed_complexity_filter;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzzing of the kernels' wave programs (host model, tests/emu) against the oracle: random graphs in all three
 modes, random aligner configurations, random reads; stops at the first difference and prints a reproducer.
-    python tools/fuzz_emu.py [--minutes M] [--seed S] [--lanes 64|8]
+    python tools/fuzz_emu.py [--minutes M] [--seed S] [--lanes 64|8] [--labels [--branch-xdrop]]
 CPU only (test infrastructure: the oracle is the checker, the host model runs the same sources the HIP build compiles)."""
 import argparse
 import os
@@ -30,7 +30,11 @@ def main():
     ap.add_argument("--labels", action="store_true", help="campaign of label-aware alignment (LabeledAligner): BASIC graphs built from "
                     "several diverged strains, a label per strain and per genome segment, compared with the oracle's LabeledAligner "
                     "(alignment lists and their label sets)")
+    ap.add_argument("--branch-xdrop", action="store_true", help="with --labels: per-branch x-drop (global_xdrop = 0), rel_score_cutoff drawn "
+                    "from {0.95, 0.5} and max_nodes_per_seq_char from {5, 0.5}")
     args = ap.parse_args()
+    if args.branch_xdrop and not args.labels:
+        sys.exit("--branch-xdrop goes with --labels (only label-aware aligners accept global_xdrop = 0)")
     if args.lanes in ("8", "16"):
         os.environ["MGX_EMU_WAVE"] = args.lanes
     import emu_drv
@@ -197,9 +201,14 @@ def main():
                 os.environ["MGX_EMU_LABEL_SCALE"] = str(rng.choice([2, 4]))
             if rng.random() < 0.3:
                 cfg.left_end_bonus, cfg.right_end_bonus = rng.choice([0, 2, 5]), rng.choice([0, 3, 5])
+            if args.branch_xdrop:
+                cfg.global_xdrop = 0
+                cfg.rel_score_cutoff = rng.choice([0.95, 0.5])
+                cfg.max_nodes_per_seq_char = rng.choice([5.0, 0.5])
         desc = dict(seed=seed, mode=mode, k=k, mask=mask, glen=len(genome), n_seqs=len(seqs), msl=cfg.min_seed_length,
                     maxsl=cfg.max_seed_length, per_locus=cfg.max_num_seeds_per_locus, xdrop=cfg.xdrop, n_alt=cfg.num_alternative_paths,
                     fwd_rc=cfg.forward_and_reverse_complement, mem=cfg.min_exact_match,
+                    global_xdrop=cfg.global_xdrop, rel=cfg.rel_score_cutoff, nodes_per_char=cfg.max_nodes_per_seq_char,
                     env={v: os.environ.get(v) for v in ("MGX_EMU_SPLIT", "MGX_EMU_MULTIPASS", "MGX_NO_FAST", "MGX_EMU_LDS", "MGX_EMU_RESUME_CAP",
                                                          "MGX_EMU_LABEL_SCALE")})
         if args.verbose:
