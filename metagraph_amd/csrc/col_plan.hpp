@@ -1,7 +1,7 @@
 // col_plan.hpp — the host half of mgx_annotation_load_columns_device: the walk over a `.column.annodbg` image that parse_columns
 // (boss_files.hpp) makes, with the Cursor, RawVec, skip and plan functions of boss_files.hpp / dbg_plan.hpp, without decoding a
-// payload (plan_columns); and the layout of one load's device buffers and descriptor tables (ColBatch) for the kernel bodies of
-// col_decode.hpp.  Host code; used by mgx_colload.hip and by tests/emu/col_decode_check.cpp, which run the same ColBatch.
+// payload (plan_columns); the layout of a batch of bit vectors in the arena with its descriptor tables (BvBatch) for the kernel
+// bodies of bv_decode.hpp; and one load's columns as such a batch (ColBatch) for those of col_decode.hpp.  Host code; used by mgx_colload.hip and by tests/emu/col_decode_check.cpp, which run the same ColBatch.
 //
 // A plan only ever answers "decode this on the device" or "ask the host reader": whenever it throws (a ParseError / Unsupported of
 // the shared functions, or NeedsHost for the checks that parse_columns makes after it has decoded a payload), and whenever the
@@ -58,98 +58,115 @@ inline ColumnsPlan plan_columns(const uint8_t *data, size_t n) {
     return p;
 }
 
+// A batch of bit vectors for the shared stage of bv_decode.hpp: the descriptor and prefix tables, and the vectors' places in the
+// arena.  Vectors are added in label order; place() then lays the payloads out from `base` on — sections bt | btnr | low | high |
+// plain bits, each in the order of adding, each closed by two zero words —, copies them into the stage, and gives every rrr
+// vector and every sd vector that wants one a bit map from `tail` on (a stat vector's payload is its map).
+struct BvBatch {
+    std::vector<BvRrr> rrr;
+    std::vector<CdSd> sd;
+    std::vector<BvMap> map;
+    std::vector<uint64_t> rbprefix{ 0 }, hprefix{ 0 }, bmprefix{ 0 };      // rrr.size() + 1, sd.size() + 1, map.size() + 1
+    uint64_t payload_words = 10, tail_words = 0;
+    uint32_t sd_maps = 0;                         // the sd vectors that have a bit map
+    uint64_t rb_stride = 0, bm_stride = 0;        // the blocks of every rrr vector / the words of every bit map, 0: they differ (bv_find)
+    std::vector<const RrrPlan *> rrr_src;         // (host only: the payloads, in images that outlive place())
+    std::vector<const SdPlan *> sd_src;
+    std::vector<const RawVec *> map_src;          // a stat vector's bits; nullptr: a map of the tail
+    uint64_t rrr_blocks() const { return rbprefix.back(); }
+    uint64_t high_words() const { return hprefix.back(); }
+    uint64_t bm_words() const { return bmprefix.back(); }
+
+    // a vector of `bits` bits for `label`; sd_map: an sd vector gets a bit map (rrr and stat vectors always have one)
+    void add(const ColumnPlan &p, uint64_t bits, uint32_t label, bool sd_map) {
+        const uint64_t words = (bits + 63) / 64;
+        uint32_t kind = CD_KIND_STAT;
+        if (p.code == CODE_SD) {
+            kind = p.sd.inverted ? CD_KIND_SD_INVERTED : CD_KIND_SD;
+            CdSd d{};
+            d.high_bits = p.sd.high.bits; d.low_n = p.sd.low.size(); d.ones = p.sd.ones; d.wl = p.sd.wl; d.inverted = p.sd.inverted; d.label = label;
+            d.map = sd_map ? (uint32_t)map.size() : BV_NO_MAP;
+            sd.push_back(d);
+            sd_src.push_back(&p.sd);
+            hprefix.push_back(hprefix.back() + p.sd.high.words());
+            payload_words += p.sd.low.words() + p.sd.high.words();
+            sd_maps += sd_map;
+            if (!sd_map) return;
+        } else if (p.code == CODE_RRR) {
+            kind = CD_KIND_RRR;
+            BvRrr d{};
+            d.btnr_bits = p.rrr.btnr.bits; d.bits = bits; d.label = label; d.map = (uint32_t)map.size();
+            rb_stride = rrr.empty() || rb_stride == p.rrr.n_blocks ? p.rrr.n_blocks : 0;
+            rrr.push_back(d);
+            rrr_src.push_back(&p.rrr);
+            rbprefix.push_back(rbprefix.back() + p.rrr.n_blocks);
+            payload_words += p.rrr.bt.words() + p.rrr.btnr.words();
+        } else payload_words += p.stat.v.words();
+        bm_stride = map.empty() || bm_stride == words ? words : 0;
+        map.push_back(BvMap{ 0, bits, p.code == CODE_STAT ? p.stat.ones : 0, kind, label });
+        map_src.push_back(p.code == CODE_STAT ? &p.stat.v : nullptr);
+        bmprefix.push_back(bmprefix.back() + words);
+        if (p.code != CODE_STAT) tail_words += words;
+    }
+    // stage[base .. base + payload_words): zero before
+    void place(uint64_t base, uint64_t tail, uint64_t *stage) {
+        uint64_t at = base;
+        auto put = [&](const RawVec &v, uint64_t &begin) {
+            begin = at;
+            if (v.words()) memcpy(stage + at, v.src, v.words() * 8);
+            at += v.words();
+        };
+        for (size_t i = 0; i < rrr.size(); ++i) put(rrr_src[i]->bt, rrr[i].bt_begin);
+        at += 2;
+        for (size_t i = 0; i < rrr.size(); ++i) put(rrr_src[i]->btnr, rrr[i].btnr_begin);
+        at += 2;
+        for (size_t i = 0; i < sd.size(); ++i) put(sd_src[i]->low, sd[i].low_begin);
+        at += 2;
+        for (size_t i = 0; i < sd.size(); ++i) put(sd_src[i]->high, sd[i].high_begin);
+        at += 2;
+        for (size_t m = 0; m < map.size(); ++m) if (map_src[m]) put(*map_src[m], map[m].src_begin);
+        at = tail;
+        for (size_t m = 0; m < map.size(); ++m) if (!map_src[m]) { map[m].src_begin = at; at += bmprefix[m + 1] - bmprefix[m]; }
+        for (BvRrr &d : rrr) d.bm_begin = map[d.map].src_begin;
+        for (CdSd &d : sd) if (d.map != BV_NO_MAP) d.bm_begin = map[d.map].src_begin;
+    }
+};
+
 // The buffers and tables of one load (all columns of all files, side by side in argument order; every file the same n_rows).
 // arena: `upload_words` words copied from the host (stage) followed by the bit maps, which the device clears.
 struct ColBatch {
-    uint64_t n_rows = 0, W = 0, n_blocks = 0;    // W = ceil(n_rows / 64); n_blocks = ceil(n_rows / 63)
+    uint64_t n_rows = 0;
     std::vector<std::string> labels;
-    std::vector<CdRrr> rrr;
-    std::vector<CdSd> sd;
-    std::vector<CdBm> bm;
+    BvBatch v;                                    // the columns, n_rows bits each; a plain sd column has no bit map
     std::vector<CdLabel> lab;
-    std::vector<uint64_t> hprefix{ 0 };           // sd.size() + 1
     std::vector<uint32_t> file_first;             // the first label of every file
     std::vector<uint64_t> stage;                  // the uploaded part of the arena
     uint64_t upload_words = 0, arena_words = 0;
     uint64_t extra_begin = 0;                     // the first of the `extra_upload` words of build()
     bool kinds[4] = { false, false, false, false };
-    uint64_t high_words() const { return hprefix.back(); }
-    uint64_t bm_words() const { return (uint64_t)bm.size() * W; }
-    uint64_t rrr_blocks() const { return (uint64_t)rrr.size() * n_blocks; }
 
     // plans[f] over images that outlive the call.  n_rows > 0 (an empty matrix has nothing to decode).
     // extra_upload: words kept free (zero) at the end of the uploaded part for payloads of the caller's (coord_plan.hpp)
     void build(const std::vector<ColumnsPlan> &plans, uint64_t extra_upload = 0) {
         n_rows = plans[0].n_rows;
-        W = (n_rows + 63) / 64;
-        n_blocks = (n_rows + 62) / 63;
-        std::vector<const ColumnPlan *> cols;
         for (const ColumnsPlan &p : plans) {
             file_first.push_back((uint32_t)labels.size());
             labels.insert(labels.end(), p.labels.begin(), p.labels.end());
-            for (const ColumnPlan &c : p.cols) cols.push_back(&c);
-        }
-        lab.resize(cols.size());
-        for (uint32_t j = 0; j < cols.size(); ++j) {
-            const ColumnPlan &c = *cols[j];
-            CdLabel &l = lab[j];
-            l = CdLabel{ CD_KIND_SD, 0, 0, 0 };
-            if (c.code == CODE_SD) {
-                l.kind = c.sd.inverted ? CD_KIND_SD_INVERTED : CD_KIND_SD;
-                l.sd = (uint32_t)sd.size();
-                CdSd d{};
-                d.high_bits = c.sd.high.bits; d.low_n = c.sd.low.size(); d.ones = c.sd.ones; d.wl = c.sd.wl; d.inverted = c.sd.inverted; d.label = j;
-                sd.push_back(d);
-                hprefix.push_back(hprefix.back() + c.sd.high.words());
-            } else l.kind = c.code == CODE_STAT ? CD_KIND_STAT : CD_KIND_RRR;
-            kinds[l.kind] = true;
-            if (l.kind != CD_KIND_SD) {
-                l.bm = (uint32_t)bm.size();
-                bm.push_back(CdBm{ 0, c.code == CODE_STAT ? c.stat.ones : 0, l.kind, j });
-            }
-            if (c.code == CODE_RRR) {
-                CdRrr d{};
-                d.btnr_bits = c.rrr.btnr.bits; d.label = j;
-                rrr.push_back(d);
+            for (const ColumnPlan &c : p.cols) {
+                CdLabel l{ CD_KIND_SD, 0, 0, 0 };
+                if (c.code == CODE_SD) { l.kind = c.sd.inverted ? CD_KIND_SD_INVERTED : CD_KIND_SD; l.sd = (uint32_t)v.sd.size(); }
+                else l.kind = c.code == CODE_STAT ? CD_KIND_STAT : CD_KIND_RRR;
+                if (l.kind != CD_KIND_SD) l.bm = (uint32_t)v.map.size();
+                kinds[l.kind] = true;
+                v.add(c, n_rows, (uint32_t)lab.size(), c.sd.inverted);
+                lab.push_back(l);
             }
         }
-        // sections of the uploaded part: bt | btnr | low | high | plain bits, each closed by two zero words
-        uint64_t at = 0;
-        auto section = [&](auto &&span_of, auto &&note) {
-            for (uint32_t j = 0; j < cols.size(); ++j) {
-                const RawVec *v = span_of(*cols[j]);
-                if (!v) continue;
-                note(j, at);
-                at += v->words();
-            }
-            at += 2;
-        };
-        uint32_t x = 0;
-        section([](const ColumnPlan &c) { return c.code == CODE_RRR ? &c.rrr.bt : nullptr; }, [&](uint32_t, uint64_t o) { rrr[x++].bt_begin = o; });
-        x = 0;
-        section([](const ColumnPlan &c) { return c.code == CODE_RRR ? &c.rrr.btnr : nullptr; }, [&](uint32_t, uint64_t o) { rrr[x++].btnr_begin = o; });
-        section([](const ColumnPlan &c) { return c.code == CODE_SD ? &c.sd.low : nullptr; }, [&](uint32_t j, uint64_t o) { sd[lab[j].sd].low_begin = o; });
-        section([](const ColumnPlan &c) { return c.code == CODE_SD ? &c.sd.high : nullptr; }, [&](uint32_t j, uint64_t o) { sd[lab[j].sd].high_begin = o; });
-        section([](const ColumnPlan &c) { return c.code == CODE_STAT ? &c.stat.v : nullptr; }, [&](uint32_t j, uint64_t o) { bm[lab[j].bm].src_begin = o; });
-        extra_begin = at;
-        at += extra_upload;
-        upload_words = at;
+        extra_begin = v.payload_words;
+        upload_words = extra_begin + extra_upload;
+        arena_words = upload_words + v.tail_words;
         stage.assign(upload_words, 0);
-        auto copy = [&](const RawVec &v, uint64_t o) { if (v.words()) memcpy(stage.data() + o, v.src, v.words() * 8); };
-        x = 0;
-        for (uint32_t j = 0; j < cols.size(); ++j) {
-            const ColumnPlan &c = *cols[j];
-            if (c.code == CODE_RRR) { copy(c.rrr.bt, rrr[x].bt_begin); copy(c.rrr.btnr, rrr[x].btnr_begin); ++x; }
-            else if (c.code == CODE_SD) { copy(c.sd.low, sd[lab[j].sd].low_begin); copy(c.sd.high, sd[lab[j].sd].high_begin); }
-            else copy(c.stat.v, bm[lab[j].bm].src_begin);
-        }
-        // the bit maps behind them
-        x = 0;
-        for (uint32_t j = 0; j < cols.size(); ++j) {
-            if (lab[j].kind == CD_KIND_RRR) { rrr[x].bm_begin = at; bm[lab[j].bm].src_begin = at; at += W; ++x; }
-            else if (lab[j].kind == CD_KIND_SD_INVERTED) { sd[lab[j].sd].bm_begin = at; bm[lab[j].bm].src_begin = at; at += W; }
-        }
-        arena_words = at;
+        v.place(0, upload_words, stage.data());
     }
 
     // col_begin from the per-column counts; false: parse_columns' guard on the total of expanded rows (an inverted column reached

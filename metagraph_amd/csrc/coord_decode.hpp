@@ -1,19 +1,17 @@
 // coord_decode.hpp — k-mer coordinates on the device, the kernel bodies of two steps:
 //   * cq_*: the tuple section of `.column.annodbg.coords` / `.column_coord.annodbg` files (boss_files.hpp: read_tuples) decoded
-//     into the coord_begin / coords arrays of mgx_annotation_set_coordinates, batched over all columns of a load like the binary
-//     columns of col_decode.hpp, whose arena, descriptors (CdSd), error record (cd_fail) and sd / rrr bodies are used here;
+//     into the coord_begin / coords arrays of mgx_annotation_set_coordinates, batched over all columns of a load;
 //   * ct_*: mgx_annotation_set_coordinates_device, the transposition of those arrays into the row-major row_entry / coord_off /
 //     coords of the device annotation.
 // The kernels are in mgx_colload.hip and mgx_annot.hip; every body is an MGX_HD function over plain pointers, so that
 // tests/emu/coord_decode_check.cpp compiles this very file for the host, with every array at the size the driver gives it.
 //
-// A delimiter vector differs from a binary column in one thing: its length (values + set rows + 1 bits) is its column's own.  So
-// every item (an rrr block, a word of a bit map, a value) finds its column by cd_find over a prefix table, never by a division.
-// Every delimiter vector is decoded into a bit map of ceil(bits / 64) words (a stat vector's payload is its bit map), the maps
-// are ranked by one scan, and the one of rank r (0-based) at position p begins the tuple of the column's set row r at value p - r.
-// Rules as in col_decode.hpp: indices from file content are compared with their array's length before use, no trip count depends
-// on file content, a failed check records (column, check, position) and writes nothing out of range; the caller then asks the
-// host reader.
+// The delimiter vectors of a load are a second batch for the shared stage of bv_decode.hpp, after the binary columns: each has a
+// length of its own (values + set rows + 1 bits), each gets a bit map (map j is column j's), and the maps are ranked by one scan.
+// Here: what follows that stage — the conditions of read_tuples on every vector, the rank pass (the one of rank r, 0-based, at
+// position p begins the tuple of the column's set row r at value p - r) and the unpacking of the values.  Rules as in
+// bv_decode.hpp: indices from file content are compared with their array's length before use, no trip count depends on file
+// content, a failed check records (column, check, position) and writes nothing out of range; the caller then asks the host reader.
 #pragma once
 #include "col_decode.hpp"
 
@@ -27,86 +25,32 @@ enum CqCheck : uint32_t {
     CQ_CHECKS
 };
 
-// per column (= label): its delimiter vector and its values.  kind: CD_KIND_*; bits: the delimiters' length; bm_begin: the word
-// offset of the bit map in the arena; stat_ones: a stat vector's stored count; sub: its index among the rrr or among the sd delimiter vectors;
+// per column (= label), next to its delimiter vector's BvMap: sub: the vector's index among the sd vectors (sd kinds);
 // val_begin / width: the values' words in the arena and their width (value i of the column is coords[vprefix[label] + i])
-struct CqCol { uint64_t bits, bm_begin, stat_ones, val_begin; uint32_t kind, sub, width, pad; };
-static_assert(sizeof(CqCol) == 48, "CqCol");
-// per rrr delimiter vector: bt / btnr word offsets, btnr's bits, its column (its blocks: rbprefix[t] .. rbprefix[t + 1])
-struct CqRrr { uint64_t bt_begin, btnr_begin, btnr_bits; uint32_t label, pad; };
-static_assert(sizeof(CqRrr) == 32, "CqRrr");
-
-// ---- rrr delimiter vectors: global block gb, rbprefix[t] = the first block of vector t ---------------------------------------
-MGX_HD uint64_t cq_rrr_width(const uint64_t *arena, const CqRrr *rd, const uint64_t *rbprefix, uint32_t n_rrr, const uint8_t *wtab, uint64_t gb) {
-    if (gb >= rbprefix[n_rrr]) return 0;
-    const uint32_t t = cd_find(rbprefix, n_rrr, gb);
-    return wtab[dd_get(arena + rd[t].bt_begin, (gb - rbprefix[t]) * 6, 6)];
-}
-MGX_HD uint64_t cq_rrr_block(const uint64_t *arena, const CqRrr *rd, const uint64_t *rbprefix, uint32_t n_rrr, const uint64_t *off,
-                             const uint8_t *wtab, const uint64_t *C, uint64_t gb, uint64_t *err) {
-    const uint32_t t = cd_find(rbprefix, n_rrr, gb);
-    const CqRrr d = rd[t];
-    const uint64_t b = gb - rbprefix[t];
-    unsigned status;
-    const uint64_t block = dd_rrr_unrank(arena + d.bt_begin, arena + d.btnr_begin, d.btnr_bits, off[gb] - off[rbprefix[t]], wtab, C, b, &status);
-    if (status) cd_fail(err, d.label, status == 1 ? CD_RRR_EARLY : CD_RRR_CLASS, b);
-    return block;
-}
-
-// ---- bit maps: global word g of the concatenated maps, bmprefix[j] = the first word of column j ---------------------------------
-// the packed blocks of an rrr vector into its map (the other kinds: nothing)
-MGX_HD void cq_rrr_pack(uint64_t *arena, const CqCol *col, const uint64_t *bmprefix, uint32_t n_cols, const uint64_t *rbprefix,
-                        const uint64_t *blocks, uint64_t g) {
-    const uint32_t j = cd_find(bmprefix, n_cols, g);
-    const CqCol d = col[j];
-    if (d.kind != CD_KIND_RRR) return;
-    arena[d.bm_begin + (g - bmprefix[j])] = dd_rrr_pack(blocks + rbprefix[d.sub], rbprefix[d.sub + 1] - rbprefix[d.sub], d.bits, g - bmprefix[j]);
-}
-// sd vectors (plain and inverted): word gw of the concatenated high parts; every stored position into the vector's cleared map
-MGX_HD void cq_sd_word(uint64_t *arena, const CdSd *sd, const CqCol *col, const uint64_t *hprefix, uint32_t n_sd, const uint64_t *hrank, uint64_t gw,
-                       uint64_t *err) {
-    const uint32_t s = cd_find(hprefix, n_sd, gw);
-    const CdSd d = sd[s];
-    cd_sd_each(arena, d, gw - hprefix[s], hrank[gw] - hrank[hprefix[s]], col[d.label].bits, err, [&](uint64_t, uint64_t v) {
-        cd_set_bit(arena + d.bm_begin + (v >> 6), (unsigned)(v & 63));
-        return true;
-    });
-}
-// word w of column j's delimiters: an inverted vector's map complemented, nothing behind the last bit
-MGX_HD uint64_t cq_bm_word(const uint64_t *arena, const CqCol &d, uint64_t w) {
-    uint64_t x = arena[d.bm_begin + w];
-    if (d.kind == CD_KIND_SD_INVERTED) x = ~x;
-    const uint64_t left = d.bits - w * 64;                                 // >= 1
-    return left >= 64 ? x : x & ((1ull << left) - 1);
-}
-// cnt[g], g <= bmprefix[n_cols] (the last: the zero that closes the scan)
-MGX_HD uint64_t cq_bm_popcount(const uint64_t *arena, const CqCol *col, const uint64_t *bmprefix, uint32_t n_cols, uint64_t g) {
-    if (g >= bmprefix[n_cols]) return 0;
-    const uint32_t j = cd_find(bmprefix, n_cols, g);
-    return (uint64_t)__builtin_popcountll(cq_bm_word(arena, col[j], g - bmprefix[j]));
-}
+struct CqCol { uint64_t val_begin; uint32_t width, sub; };
+static_assert(sizeof(CqCol) == 16, "CqCol");
 // per column, after the scan: the conditions of read_tuples on a delimiter vector (its length against the values: the plan)
-MGX_HD void cq_check(const uint64_t *arena, const CqCol *col, const CdSd *sd, const uint64_t *hprefix, const uint64_t *hrank,
+MGX_HD void cq_check(const uint64_t *arena, const BvMap *map, const CqCol *col, const CdSd *sd, const uint64_t *hprefix, const uint64_t *hrank,
                      const uint64_t *bmprefix, const uint64_t *bscan, const uint64_t *col_begin, uint32_t j, uint64_t *err) {
-    const CqCol d = col[j];
+    const BvMap d = map[j];
     const uint64_t ones = bscan[bmprefix[j + 1]] - bscan[bmprefix[j]];
     if (d.kind == CD_KIND_SD || d.kind == CD_KIND_SD_INVERTED) {           // read_sd_vector: ones against popcount(high); a position twice
-        const uint64_t s = d.sub, m = hrank[hprefix[s + 1]] - hrank[hprefix[s]];
+        const uint64_t s = col[j].sub, m = hrank[hprefix[s + 1]] - hrank[hprefix[s]];
         if (m != sd[s].ones) cd_fail(err, j, CD_SD_SELECT, m);
         if (ones != (d.kind == CD_KIND_SD ? m : d.bits - m)) cd_fail(err, j, CD_SD_ORDER, ones);
     }
     if (d.kind == CD_KIND_STAT && ones != d.stat_ones) cd_fail(err, j, CD_STAT_ONES, ones);
     if (ones != col_begin[j + 1] - col_begin[j] + 1) cd_fail(err, j, CQ_ONES, ones);
-    if (!(cq_bm_word(arena, d, 0) & 1)) cd_fail(err, j, CQ_FIRST, 0);
-    if (!((cq_bm_word(arena, d, (d.bits - 1) >> 6) >> ((d.bits - 1) & 63)) & 1)) cd_fail(err, j, CQ_LAST, d.bits - 1);
+    if (!(bv_map_word(arena, d, 0) & 1)) cd_fail(err, j, CQ_FIRST, 0);
+    if (!((bv_map_word(arena, d, (d.bits - 1) >> 6) >> ((d.bits - 1) & 63)) & 1)) cd_fail(err, j, CQ_LAST, d.bits - 1);
 }
 // the rank pass: the one of rank i of column j at position p begins the tuple of entry col_begin[j] + i at value vprefix[j] + p - i;
 // the column's last one (i = its set rows) closes the last tuple: written by the last column only, as coord_begin[n_entries]
-MGX_HD void cq_rank(const uint64_t *arena, const CqCol *col, const uint64_t *bmprefix, uint32_t n_cols, const uint64_t *bscan,
+MGX_HD void cq_rank(const uint64_t *arena, const BvMap *map, const uint64_t *bmprefix, uint32_t n_cols, const uint64_t *bscan,
                     const uint64_t *col_begin, const uint64_t *vprefix, uint64_t g, uint64_t *coord_begin, uint64_t *err) {
     const uint32_t j = cd_find(bmprefix, n_cols, g);
     const uint64_t w = g - bmprefix[j], n_set = col_begin[j + 1] - col_begin[j];
-    uint64_t x = cq_bm_word(arena, col[j], w), i = bscan[g] - bscan[bmprefix[j]];
+    uint64_t x = bv_map_word(arena, map[j], w), i = bscan[g] - bscan[bmprefix[j]];
     for (unsigned t = 0; t < 64 && x; ++t, ++i, x &= x - 1) {
         if (i > n_set) { cd_fail(err, j, CD_OUT_RANGE, w); return; }
         const uint64_t p = w * 64 + (uint64_t)__builtin_ctzll(x);

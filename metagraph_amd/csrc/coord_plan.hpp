@@ -1,7 +1,7 @@
 // coord_plan.hpp — the host half of mgx_annotation_load_coord_columns_device: the walk over the tuple section that read_tuples
 // (boss_files.hpp) makes, and over a `.column_coord.annodbg` image as parse_column_coord makes it, without decoding a payload; and
-// the layout of the coordinate part of one load's arena and its descriptor tables (CoordBatch) for the cq_* bodies of
-// coord_decode.hpp.  Host code; used by mgx_colload.hip and tests/emu/coord_decode_check.cpp, which run the same batch.
+// the layout of the coordinate part of one load's arena and its tables (CoordBatch: the delimiter vectors as a BvBatch of
+// col_plan.hpp, and the values) for the cq_* bodies of coord_decode.hpp.  Host code; used by mgx_colload.hip and tests/emu/coord_decode_check.cpp, which run the same batch.
 // As in col_plan.hpp a plan answers "decode this on the device" or "ask the host reader" (any exception), nothing else.
 #pragma once
 #include "col_plan.hpp"
@@ -10,9 +10,7 @@
 namespace mgx { namespace files {
 
 // one column of the tuple section: the delimiters (a bit_vector_smart: code + vector) and the values (sdsl::int_vector<>)
-struct TuplePlan {
-    uint64_t code = CODE_SD;
-    SdPlan sd; StatPlan stat; RrrPlan rrr;
+struct TuplePlan : ColumnPlan {
     RawVec values;
     uint64_t bits() const { return code == CODE_SD ? sd.size : code == CODE_STAT ? stat.v.bits : rrr.bits; }
 };
@@ -72,92 +70,41 @@ inline ColumnsPlan plan_column_coord(const uint8_t *data, size_t n, std::vector<
 }
 
 // The coordinate part of one load: all columns of all files in argument order, like ColBatch.  Its payloads lie in the arena's
-// uploaded part at [base, base + upload_words) — sections bt | btnr | low | high | plain bits | values, each closed by two zero
-// words —, the bit maps of the sd and rrr delimiter vectors behind everything else at [tail, tail + tail_words).
+// uploaded part at [base, base + upload_words) — the sections of the delimiter vectors (BvBatch: every one gets a bit map), then
+// the values, closed by two zero words —, the bit maps of the sd and rrr delimiter vectors behind everything else at
+// [tail, tail + v.tail_words).
 struct CoordBatch {
+    BvBatch v;                                    // the delimiter vectors; map j is column j's
     std::vector<CqCol> col;
-    std::vector<CqRrr> rrr;
-    std::vector<CdSd> sd;
-    std::vector<uint64_t> hprefix{ 0 }, rbprefix{ 0 }, bmprefix{ 0 }, vprefix{ 0 };
-    uint64_t upload_words = 0, tail_words = 0;
-    bool any_sd() const { return !sd.empty(); }
-    uint64_t high_words() const { return hprefix.back(); }
-    uint64_t rrr_blocks() const { return rbprefix.back(); }
-    uint64_t bm_words() const { return bmprefix.back(); }
+    std::vector<uint64_t> vprefix{ 0 };
+    uint64_t upload_words = 0;
     uint64_t n_values() const { return vprefix.back(); }
 
-    // the tables, with offsets relative to base / tail (place() makes them absolute)
     void layout(const std::vector<const TuplePlan *> &t) {
-        col.resize(t.size());
+        upload_words = 2;
         for (uint32_t j = 0; j < t.size(); ++j) {
-            const TuplePlan &p = *t[j];
-            CqCol &c = col[j];
-            c = CqCol{ p.bits(), 0, 0, 0, CD_KIND_SD, 0, p.values.width, 0 };
-            if (p.code == CODE_SD) {
-                c.kind = p.sd.inverted ? CD_KIND_SD_INVERTED : CD_KIND_SD;
-                c.sub = (uint32_t)sd.size();
-                CdSd d{};
-                d.high_bits = p.sd.high.bits; d.low_n = p.sd.low.size(); d.ones = p.sd.ones; d.wl = p.sd.wl; d.inverted = p.sd.inverted; d.label = j;
-                sd.push_back(d);
-                hprefix.push_back(hprefix.back() + p.sd.high.words());
-            } else if (p.code == CODE_STAT) { c.kind = CD_KIND_STAT; c.stat_ones = p.stat.ones; }
-            else {
-                c.kind = CD_KIND_RRR;
-                c.sub = (uint32_t)rrr.size();
-                CqRrr d{};
-                d.btnr_bits = p.rrr.btnr.bits; d.label = j;
-                rrr.push_back(d);
-                rbprefix.push_back(rbprefix.back() + p.rrr.n_blocks);
-            }
-            bmprefix.push_back(bmprefix.back() + (c.bits + 63) / 64);
-            vprefix.push_back(vprefix.back() + p.values.size());
+            col.push_back(CqCol{ 0, t[j]->values.width, (uint32_t)v.sd.size() });
+            v.add(*t[j], t[j]->bits(), j, true);
+            vprefix.push_back(vprefix.back() + t[j]->values.size());
+            upload_words += t[j]->values.words();
         }
-        uint64_t at = 0;
-        auto section = [&](auto &&span_of, auto &&note) {
-            for (uint32_t j = 0; j < t.size(); ++j) {
-                const RawVec *v = span_of(*t[j]);
-                if (!v) continue;
-                note(j, at);
-                at += v->words();
-            }
-            at += 2;
-        };
-        section([](const TuplePlan &p) { return p.code == CODE_RRR ? &p.rrr.bt : nullptr; }, [&](uint32_t j, uint64_t o) { rrr[col[j].sub].bt_begin = o; });
-        section([](const TuplePlan &p) { return p.code == CODE_RRR ? &p.rrr.btnr : nullptr; }, [&](uint32_t j, uint64_t o) { rrr[col[j].sub].btnr_begin = o; });
-        section([](const TuplePlan &p) { return p.code == CODE_SD ? &p.sd.low : nullptr; }, [&](uint32_t j, uint64_t o) { sd[col[j].sub].low_begin = o; });
-        section([](const TuplePlan &p) { return p.code == CODE_SD ? &p.sd.high : nullptr; }, [&](uint32_t j, uint64_t o) { sd[col[j].sub].high_begin = o; });
-        section([](const TuplePlan &p) { return p.code == CODE_STAT ? &p.stat.v : nullptr; }, [&](uint32_t j, uint64_t o) { col[j].bm_begin = o; });
-        section([](const TuplePlan &p) { return &p.values; }, [&](uint32_t j, uint64_t o) { col[j].val_begin = o; });
-        upload_words = at;
-        at = 0;
-        for (uint32_t j = 0; j < t.size(); ++j)
-            if (col[j].kind != CD_KIND_STAT) {
-                col[j].bm_begin = at;
-                if (col[j].kind != CD_KIND_RRR) sd[col[j].sub].bm_begin = at;
-                at += (col[j].bits + 63) / 64;
-            }
-        tail_words = at;
+        upload_words += v.payload_words;
     }
-    // the payloads into stage[base .. base + upload_words) (zero before) and every offset made absolute
+    // the payloads into stage[base .. base + upload_words) (zero before)
     void place(const std::vector<const TuplePlan *> &t, uint64_t base, uint64_t tail, uint64_t *stage) {
-        auto copy = [&](const RawVec &v, uint64_t o) { if (v.words()) memcpy(stage + base + o, v.src, v.words() * 8); };
+        v.place(base, tail, stage);
+        uint64_t at = base + v.payload_words;
         for (uint32_t j = 0; j < t.size(); ++j) {
-            const TuplePlan &p = *t[j];
-            CqCol &c = col[j];
-            if (p.code == CODE_RRR) { copy(p.rrr.bt, rrr[c.sub].bt_begin); copy(p.rrr.btnr, rrr[c.sub].btnr_begin); }
-            else if (p.code == CODE_SD) { copy(p.sd.low, sd[c.sub].low_begin); copy(p.sd.high, sd[c.sub].high_begin); }
-            else copy(p.stat.v, c.bm_begin);
-            copy(p.values, c.val_begin);
-            c.val_begin += base;
-            c.bm_begin += c.kind == CD_KIND_STAT ? base : tail;
+            const RawVec &x = t[j]->values;
+            col[j].val_begin = at;
+            if (x.words()) memcpy(stage + at, x.src, x.words() * 8);
+            at += x.words();
         }
-        for (CqRrr &d : rrr) { d.bt_begin += base; d.btnr_begin += base; }
-        for (CdSd &d : sd) { d.low_begin += base; d.high_begin += base; d.bm_begin += tail; }
     }
     // read_tuples' first condition, once the columns' set rows are counted: bits = values + set rows + 1
     bool lengths_fit(const std::vector<uint64_t> &col_begin) const {
         for (uint32_t j = 0; j < col.size(); ++j)
-            if (col[j].bits != (vprefix[j + 1] - vprefix[j]) + (col_begin[j + 1] - col_begin[j]) + 1) return false;
+            if (v.map[j].bits != (vprefix[j + 1] - vprefix[j]) + (col_begin[j + 1] - col_begin[j]) + 1) return false;
         return true;
     }
 };

@@ -1,6 +1,6 @@
 // tests/emu/coord_decode_check.cpp — TEST ONLY: metagraph_amd/csrc/coord_decode.hpp (the kernel bodies behind
-// mgx_annotation_load_coord_columns_device and mgx_annotation_set_coordinates_device) and the col_decode.hpp bodies they follow,
-// run on the host, one call per item in the order of the launches of mgx_colload.hip and mgx_annot.hip, over the plans and batch
+// mgx_annotation_load_coord_columns_device and mgx_annotation_set_coordinates_device) behind the stages of bv_stage.hpp, run on
+// the host, one call per item in the order of the launches of mgx_colload.hip and mgx_annot.hip, over the plans and batch
 // layouts of col_plan.hpp / coord_plan.hpp.  Every array has exactly the size the driver gives its device buffer; built by
 // tests/test_coord_decode_model.py (with -fsanitize=address,undefined an access outside a buffer stops the program).
 // usage: coord_decode_check OUT.bin IN [IN ...] [-- OUT.bin IN ...]; IN: `.column.annodbg` files with their `.coords` side files
@@ -10,23 +10,13 @@
 //   plan or a check asks for it — or "internal <message>" where the device path refuses what the host reader accepts, or where
 //   the transposition's tables differ from the ones mgx_annotation_set_coordinates builds.
 #include "wave.hpp"
+#include "bv_stage.hpp"
 #include "../../metagraph_amd/csrc/column_file.hpp"
 #include "../../metagraph_amd/csrc/coord_plan.hpp"
 
 #include <algorithm>
 #include <cstdio>
 #include <string>
-#include <vector>
-
-using namespace mgx;
-using namespace mgx::files;
-
-typedef std::vector<uint64_t> Words;
-
-static void scan(Words &d) {
-    uint64_t s = 0;
-    for (uint64_t &x : d) { const uint64_t c = x; x = s; s += c; }
-}
 
 // mgx_column_coord_file_read
 static ColumnFile host_read(const std::vector<std::string> &paths) {
@@ -159,78 +149,33 @@ static void one(const std::string &out_path, const std::vector<std::string> &pat
     }
     images.clear();
     sides.clear();
-    const uint32_t n_labels = (uint32_t)b.lab.size(), n_sd = (uint32_t)b.sd.size();
-    const uint64_t HW = b.high_words(), BW = b.bm_words(), RB = b.rrr_blocks();
     uint64_t err = DD_NO_ERROR;
-    Words arena(b.arena_words + cq.tail_words, 0);
+    Words arena(b.arena_words + cq.v.tail_words, 0);
     if (b.upload_words) memcpy(arena.data(), b.stage.data(), b.upload_words * 8);
     uint64_t *A = arena.data();
-    const auto &C = binomial63().c;
-    std::vector<uint8_t> wtab(64);
-    Words binom(DD_BINOM_ENTRIES);
-    for (unsigned k = 0; k < 64; ++k) wtab[k] = (k == 0 || k == 63) ? 0 : (uint8_t)(64 - __builtin_clzll(C[63][k]));
-    for (unsigned n = 0; n < 63; ++n) for (unsigned j = 0; j < 32; ++j) binom[n * 32 + j] = C[n][j];
-    // ---- the binary columns (mgx_colload.hip: decode_files, as tests/emu/col_decode_check.cpp) ----
-    const std::vector<CdRrr> rd(b.rrr);
-    const std::vector<CdSd> sd(b.sd);
-    const std::vector<CdBm> bm(b.bm);
-    const std::vector<CdLabel> lab(b.lab);
-    const Words hprefix(b.hprefix);
-    Words hrank(HW + 1), bscan(BW + 1), counts(n_labels);
-    if (RB) {
-        Words off(RB + 1), blocks(RB);
-        for (uint64_t gb = 0; gb <= RB; ++gb) off[gb] = cd_rrr_width(A, rd.data(), wtab.data(), gb, b.n_blocks, rd.size());
-        scan(off);
-        for (uint64_t gb = 0; gb < RB; ++gb) blocks[gb] = cd_rrr_block(A, rd.data(), off.data(), wtab.data(), binom.data(), gb, b.n_blocks, &err);
-        for (uint64_t g = 0; g < rd.size() * b.W; ++g) cd_rrr_pack(A, rd.data(), blocks.data(), g, b.W, b.n_blocks, b.n_rows);
-    }
-    if (n_sd) {
-        for (uint64_t gw = 0; gw <= HW; ++gw) hrank[gw] = cd_high_popcount(A, sd.data(), hprefix.data(), n_sd, gw);
-        scan(hrank);
-        if (b.kinds[CD_KIND_SD_INVERTED])
-            for (uint64_t gw = 0; gw < HW; ++gw) cd_sd_word(A, sd.data(), hprefix.data(), n_sd, hrank.data(), gw, b.n_rows, 0, nullptr, nullptr, &err);
-    }
-    if (BW) {
-        for (uint64_t g = 0; g <= BW; ++g) bscan[g] = cd_bm_popcount(A, bm.data(), g, bm.size(), b.W, b.n_rows, &err);
-        scan(bscan);
-    }
-    for (uint32_t j = 0; j < n_labels; ++j)
-        counts[j] = cd_count(lab.data(), sd.data(), bm.data(), hprefix.data(), hrank.data(), bscan.data(), j, b.W, b.n_rows, &err);
+    BvHost d(b.v);
+    bv_stage(A, b.v, d, &err);
+    const Words counts = col_counts(A, b, d, &err);
     ColumnFile f;
     if (err == DD_NO_ERROR && !b.col_begin_from(counts, f.col_begin)) { host_answer(paths, "more than 2^33 expanded rows"); return; }
     if (err == DD_NO_ERROR && !cq.lengths_fit(f.col_begin)) { host_answer(paths, "delimiters: length"); return; }
     if (err == DD_NO_ERROR) {
         f.rows.resize(f.col_begin.back());
         const Words cb(f.col_begin);
-        if (b.kinds[CD_KIND_SD])
-            for (uint64_t gw = 0; gw < HW; ++gw) cd_sd_word(A, sd.data(), hprefix.data(), n_sd, hrank.data(), gw, b.n_rows, 1, cb.data(), f.rows.data(), &err);
-        for (uint64_t g = 0; g < BW; ++g) cd_bm_extract(A, bm.data(), bscan.data(), g, b.W, b.n_rows, cb.data(), f.rows.data(), &err);
-        // ---- the tuple sections ----
-        const uint32_t n_cols = (uint32_t)cq.col.size(), q_sd = (uint32_t)cq.sd.size(), q_rrr = (uint32_t)cq.rrr.size();
-        const uint64_t CH = cq.high_words(), CB = cq.bm_words(), CR = cq.rrr_blocks(), NV = cq.n_values();
+        col_rows(A, b, d, cb, f.rows.data(), &err);
+        // ---- the tuple sections (decode_coords) ----
+        const uint32_t n_cols = (uint32_t)cq.col.size();
+        const uint64_t NV = cq.n_values();
         const std::vector<CqCol> qcol(cq.col);
-        const std::vector<CqRrr> qrrr(cq.rrr);
-        const std::vector<CdSd> qsd(cq.sd);
-        const Words qh(cq.hprefix), qrb(cq.rbprefix), qbm(cq.bmprefix), qv(cq.vprefix);
-        Words qhrank(CH + 1), qbscan(CB + 1);
-        if (CR) {
-            Words off(CR + 1), blocks(CR);
-            for (uint64_t gb = 0; gb <= CR; ++gb) off[gb] = cq_rrr_width(A, qrrr.data(), qrb.data(), q_rrr, wtab.data(), gb);
-            scan(off);
-            for (uint64_t gb = 0; gb < CR; ++gb) blocks[gb] = cq_rrr_block(A, qrrr.data(), qrb.data(), q_rrr, off.data(), wtab.data(), binom.data(), gb, &err);
-            for (uint64_t g = 0; g < CB; ++g) cq_rrr_pack(A, qcol.data(), qbm.data(), n_cols, qrb.data(), blocks.data(), g);
-        }
-        if (q_sd) {
-            for (uint64_t gw = 0; gw <= CH; ++gw) qhrank[gw] = cd_high_popcount(A, qsd.data(), qh.data(), q_sd, gw);
-            scan(qhrank);
-            for (uint64_t gw = 0; gw < CH; ++gw) cq_sd_word(A, qsd.data(), qcol.data(), qh.data(), q_sd, qhrank.data(), gw, &err);
-        }
-        for (uint64_t g = 0; g <= CB; ++g) qbscan[g] = cq_bm_popcount(A, qcol.data(), qbm.data(), n_cols, g);
-        scan(qbscan);
-        for (uint32_t j = 0; j < n_cols; ++j) cq_check(A, qcol.data(), qsd.data(), qh.data(), qhrank.data(), qbm.data(), qbscan.data(), cb.data(), j, &err);
+        const Words qv(cq.vprefix);
+        BvHost q(cq.v);
+        bv_stage(A, cq.v, q, &err);
+        for (uint32_t j = 0; j < n_cols; ++j)
+            cq_check(A, q.map.data(), qcol.data(), q.sd.data(), q.hprefix.data(), q.hrank.data(), q.bmprefix.data(), q.bscan.data(), cb.data(), j, &err);
         f.coord_begin.assign(f.rows.size() + 1, ~0ull);
         f.coords.assign(NV, -1);
-        for (uint64_t g = 0; g < CB; ++g) cq_rank(A, qcol.data(), qbm.data(), n_cols, qbscan.data(), cb.data(), qv.data(), g, f.coord_begin.data(), &err);
+        for (uint64_t g = 0; g < q.BW; ++g)
+            cq_rank(A, q.map.data(), q.bmprefix.data(), n_cols, q.bscan.data(), cb.data(), qv.data(), g, f.coord_begin.data(), &err);
         for (uint64_t o = 0; o < NV; ++o) cq_unpack(A, qcol.data(), qv.data(), n_cols, o, f.coords.data(), &err);
     }
     if (err != DD_NO_ERROR) {
