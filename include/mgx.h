@@ -411,7 +411,11 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   ext64=0|1|2          small batches on the one-read-per-wavefront 64-lane kernel (default 1) or on the 8-lane groups;
  *                        label-aware aligners: 2 = every batch on the 64-lane labeled kernel
  *   groups_per_wave=n    8-lane kernel: n = 1 .. 8 groups of a wavefront take reads, 0 = all (default: from the batch size)
- *   multi_pass=0|1       one extension per read and launch (default: automatic from the seeds per read)
+ *   multi_pass=0|1       the multi-pass extension: a launch extends a limited number of seeds per read (1, then 4, then 16, from
+ *                        pass 24 on all), unfinished reads go on in the next launch from a resume record (default: automatic
+ *                        from the seeds per read)
+ *   resume_cap=n         multi-pass extension: at most n resume records per pass (default -1: one per read, memory permitting);
+ *                        a read that finds no room for a record goes on without a seed limit in the same launch
  *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic).  1 means "where the configuration
  *                        allows it": an aligner with global_xdrop = 0 (per-branch x-drop) never runs it, nor its exact exit below —
  *                        the lane kernels encode the global rule (mgx_stats: n_lane_reads and both exact counters stay 0)

@@ -17,6 +17,13 @@ inline uint32_t post_chain_capacity(uint64_t num_alternative_paths) {
     return 4u * (uint32_t)MGX_MAX_ALTERNATIVE_PATHS - 3u * (uint32_t)std::min<uint64_t>(num_alternative_paths, MGX_MAX_ALTERNATIVE_PATHS);
 }
 
+// Multi-pass extension (extend_multi_pass in mgx.hip, and the host model's loop): seeds a read may extend in pass `pass` before it
+// has to write a resume record.  Later passes take more seeds per read, so that the number of launches stays small; 0 = no limit,
+// which makes pass 24 the last one.
+inline uint32_t multi_pass_seed_limit(uint32_t pass) {
+    return pass < 8 ? 1u : pass < 16 ? 4u : pass < 24 ? 16u : 0u;
+}
+
 inline bool check_config_scores(const mgx_config &c) {
     // aligner_config.cpp:39-66
     int8_t min_penalty = INT8_MAX;

@@ -283,6 +283,8 @@ struct mgx_aligner {
         int ext64 = 1;            // 0: never the 64-lane one-read-per-wavefront kernel (small batches run the 8-lane groups)
         int groups_per_wave = -1; // 0 = all 8 groups of a wavefront take reads, 1 .. 8 = that many
         int multi_pass = -1;      // multi-pass extension on / off
+        int resume_cap = -1;      // ... resume records a pass may write at most (-1: as many as reads, memory permitting); a read
+                                  // that finds no room goes on without a seed limit in the same launch
         int no_compact = 0, no_alias = 0, no_bt_runs = 0, no_flat = 0;
         int lane = -1;            // the lane-per-read kernel in front of the extension kernel: -1 auto, 0 off, 1 forced
         int exact = -1;           // the lane kernel's exact exit (k_lane_exact, no DP): -1 auto (level 2 for the batches the lane kernel

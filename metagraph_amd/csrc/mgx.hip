@@ -746,6 +746,7 @@ static int extend_multi_pass(mgx_aligner *A, AlignPlan &pl) {
     const uint64_t have = A->resume_pool[0].bytes + A->resume_pool[1].bytes;
     uint64_t cap = std::min<uint64_t>(n, ((uint64_t)fb / 2 + have) / (2ull * rb));      // two pools
     if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
+    if (A->opt.resume_cap >= 0) cap = std::min<uint64_t>(cap, (uint64_t)A->opt.resume_cap);      // (option resume_cap: fewer records than that)
     if (cap == 0) {               // (no room for resume records: every seed of a read in one launch)
         HIP_TRY((hipError_t)launch_extension(A, pl));
         return MGX_OK;
@@ -764,8 +765,7 @@ static int extend_multi_pass(mgx_aligner *A, AlignPlan &pl) {
         P.resume_out = A->resume_pool[out].as<uint8_t>();
         P.retry_list = lists[out]->as<uint32_t>();
         P.retry_key = A->retry_key[out].as<uint32_t>();
-        // later passes take more seeds per read, so that the number of launches stays small
-        P.seed_limit = pass < 8 ? 1 : pass < 16 ? 4 : pass < 24 ? 16 : 0;
+        P.seed_limit = multi_pass_seed_limit(pass);
         HIP_TRY((hipError_t)launch_extension(A, pl));
         unsigned long long c = 0;
         HIP_TRY(copy_sync(A, &c, cursor(A, CUR_RETRY), 8, hipMemcpyDeviceToHost));     // (synchronises with the pass)
@@ -930,6 +930,7 @@ int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
         if (key == "ext64") o.ext64 = v;
         else if (key == "groups_per_wave") o.groups_per_wave = std::min(8, v);
         else if (key == "multi_pass") o.multi_pass = v;
+        else if (key == "resume_cap") o.resume_cap = std::max(-1, v);
         else if (key == "no_compact") o.no_compact = v;
         else if (key == "decode_on_device") o.decode_on_device = v != 0;
         else if (key == "no_alias") o.no_alias = v;

@@ -42,6 +42,7 @@ struct EmuRun {
     DevLimits lim;
     KernelStats stats;
     uint64_t retried = 0;         // reads handed to pass 2 of the two-pass extension
+    std::vector<uint64_t> pass_items;      // multi-pass extension: the work items of each pass that ran
     uint64_t out_used = 0;        // words of `stream` in use
     uint64_t lane_done = 0, lane_ran = 0;     // MGX_EMU_LANE: reads the lane-per-read path finished; whether it ran at all
     uint64_t lane_bail[32] = { 0 };            // ... and why it sent the others on (LANE_BAIL codes)
@@ -578,22 +579,28 @@ void *emu_align_anno(void *gh, void *anno, const mgx_config *config, const mgx_l
             // label-aware alignment: one pass, no seed limit (the per-read program)
             for (uint64_t i = 0; i < n_ext; ++i) run_extend(order[i], nullptr);
         } else if (mp && *mp == '1') {
-            // the product's multi-pass extension: one seed per read and pass, resume records in between, the retry positions
-            // of a pass sorted by their work key for the next one (MGX_EMU_RESUME_CAP: records a pass may write)
+            // the product's multi-pass extension: a limited number of seeds per read and pass, resume records in between, the
+            // retry positions of a pass sorted by their work key for the next one (MGX_EMU_RESUME_CAP: records a pass may write)
             const uint32_t rb = resume_rec_bytes(R->lim, std::max<uint32_t>(1, (uint32_t)cfg.num_alternative_paths));
             const char *cap_env = getenv("MGX_EMU_RESUME_CAP");
             const uint32_t cap = cap_env ? (uint32_t)atoi(cap_env) : (uint32_t)n;
             std::vector<uint8_t> pool_a((size_t)rb * std::max<uint32_t>(cap, 1)), pool_b((size_t)rb * std::max<uint32_t>(cap, 1));
             std::vector<uint32_t> list_a(n + 1), list_b(n + 1), key_a(n + 1), key_b(n + 1), ord(n + 1);
-            P.seed_limit = 1; P.resume_rec_bytes = rb; P.resume_cap = cap;
+            // (the seed limit of a pass is the product's, multi_pass_seed_limit: 0 from pass 24 on, which ends the loop as it
+            // ends extend_multi_pass)
+            P.seed_limit = multi_pass_seed_limit(0); P.resume_rec_bytes = rb; P.resume_cap = cap;
             P.retry_list = list_a.data(); P.retry_key = key_a.data(); P.retry_count = &retry_count; P.resume_out = pool_a.data();
             for (uint64_t i = 0; i < n_ext; ++i)
                 run_extend(order[i], nullptr);
             R->retried = retry_count;
+            R->pass_items.push_back(n_ext);
             std::vector<uint8_t> *pin = &pool_a, *pout = &pool_b;
             std::vector<uint32_t> *lin = &list_a, *lout = &list_b, *kin = &key_a, *kout = &key_b;
-            for (int pass = 1; retry_count; ++pass) {
+            for (uint32_t pass = 1;; ++pass) {
                 const uint64_t c = std::min<uint64_t>(retry_count, cap);
+                if (c == 0 || P.seed_limit == 0) break;
+                P.seed_limit = multi_pass_seed_limit(pass);
+                R->pass_items.push_back(c);
                 for (uint64_t i = 0; i < c; ++i) ord[i] = (uint32_t)i;
                 std::stable_sort(ord.begin(), ord.begin() + c, [&](uint32_t a, uint32_t b) { return (*kin)[a] < (*kin)[b]; });
                 retry_count = 0;
@@ -658,6 +665,12 @@ void emu_raw(void *r, const void **headers, uint64_t *n, const uint32_t **stream
     *stream = R->stream.data(); *words = R->out_used;
 }
 uint64_t emu_retried(void *r) { return static_cast<EmuRun *>(r)->retried; }
+// MGX_EMU_MULTIPASS=1 runs: the number of passes that ran; out[p] = the work items of pass p, for p < cap
+uint64_t emu_pass_items(void *r, uint64_t *out, uint64_t cap) {
+    auto &v = static_cast<EmuRun *>(r)->pass_items;
+    for (uint64_t p = 0; p < cap && p < v.size(); ++p) out[p] = v[p];
+    return v.size();
+}
 const char *emu_error(void *r) { return static_cast<EmuRun *>(r)->error.c_str(); }
 void emu_results(void *r, mgx_results *out) { static_cast<EmuRun *>(r)->host.view(out); }
 void emu_mapping(void *r, mgx_mapping *out) {

@@ -147,6 +147,16 @@ class EmuRun:
         L().emu_retried.argtypes = [C.c_void_p]
         return L().emu_retried(self.r)
 
+    def pass_items(self):
+        """MGX_EMU_MULTIPASS=1 runs: the work items of each pass of the multi-pass extension that ran (pass 0: the batch's reads
+        that reach the extension; later: the resume records of the pass before).  Its length is the number of passes."""
+        L().emu_pass_items.restype = C.c_uint64
+        L().emu_pass_items.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64]
+        n = L().emu_pass_items(self.r, None, 0)
+        a = (C.c_uint64 * max(1, n))()
+        L().emu_pass_items(self.r, a, n)
+        return [int(a[i]) for i in range(n)]
+
     def raw(self):
         """-> (headers bytes, stream bytes): the device-layout records mgx_device_results exposes on the GPU"""
         hp, n, sp, w = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
