@@ -110,9 +110,11 @@ typedef struct mgx_config {
     uint8_t chain_alignments;          /* :49 (must be 0.  The reference never lets a caller set it either: it exits without coordinates,
                                         * dbg_aligner.cpp:546-550, and LabeledAligner switches it on itself for an annotation with
                                         * coordinates, aligner_labeled.cpp:457-462 — such annotations are refused at
-                                        * mgx_labeled_aligner_create.  Of seed chaining, aligner_chainer.cpp:47-542, the device has the
-                                        * chainer's DP, mgx_chain_seeds, and k-mer coordinates, mgx_annotation_set_coordinates; the
-                                        * extension between chained seeds is not built: DESIGN 3.9) */
+                                        * mgx_labeled_aligner_create.  Of seed chaining, aligner_chainer.cpp:47-542, the device has
+                                        * k-mer coordinates, mgx_annotation_set_coordinates, the chainer's DP on its own,
+                                        * mgx_chain_seeds, and the whole chain stage of a read batch — seeds, their coordinate-aware
+                                        * filter, the anchors, the chainer's tables —, mgx_chain_tables_batch on a handle of
+                                        * mgx_seed_chainer_create; the extension between chained seeds is not built: DESIGN 3.9) */
     uint8_t post_chain_alignments;     /* :50: chain_alignments (aligner_chainer.cpp:555-720) over every query's alignments.  The
                                         * device then keeps EVERY alignment of a query (aligner_aggregator.hpp:88-96; at most
                                         * 4 x MGX_MAX_ALTERNATIVE_PATHS - 3 x num_alternative_paths = 13 with the default of
@@ -508,8 +510,10 @@ size_t mgx_format_json(const mgx_results *res, uint64_t query_index, const char 
  * annotation/binary_matrix/column_sparse/column_major.cpp:27-44 — 1000 columns x |rows| random bit tests in the reference).
  * Label coordinates: read from `.column.annodbg.coords` / `.column_coord.annodbg` files on the host and on the device
  * (mgx_column_coord_file_read, mgx_annotation_load_coord_columns_device, "files" below), kept row-major on the device and answered by
- * mgx_annotation_get_row_tuples; the anchor DP of seed chaining is mgx_chain_seeds.  Not built: LabeledAligner's coordinate mode
- * itself, i.e. the extension half of chaining (aligner_labeled.cpp:361-448,685-700, aligner_chainer.cpp:47-339) — an annotation
+ * mgx_annotation_get_row_tuples; the anchor DP of seed chaining is mgx_chain_seeds, and the chain stage of coordinate mode for a
+ * whole read batch — both strands' seeds, filter_seeds with coordinates, the anchors, the sort and the DP, left in device memory —
+ * is mgx_chain_tables_batch (mgx_seed_chainer_create).  Not built: the rest of LabeledAligner's coordinate mode, i.e. the extension
+ * half of chaining (aligner_labeled.cpp:361-448, aligner_chainer.cpp:47-339, dbg_aligner.cpp:155-250,388-529) — an annotation
  * with coordinates is refused by mgx_labeled_aligner_create.
  *
  * mgx_annotation_create stands in for the annotator argument of LabeledAligner<>(graph, config, annotator)
@@ -542,8 +546,9 @@ int mgx_annotation_get_rows(mgx_annotation *a, const uint64_t *rows, uint64_t n,
  * mgx_annotation_create_sparse: pair x (label j = the column whose range holds x, row rows[x]) has the ascending coordinates
  * coords[coord_begin[x] .. coord_begin[x + 1]).  Host arrays.  Round 6: the annotation and its batched lookup
  * (mgx_annotation_get_row_tuples = MultiIntMatrix::get_row_tuples, what AnnotationBuffer::fetch_queued_annotations calls,
- * annotation_buffer.cpp:166-181) are on the device; LabeledAligner's coordinate mode itself (seed chaining,
- * aligner_labeled.cpp:457-462) is not — mgx_labeled_aligner_create refuses such an annotation (MGX_ERR_UNSUPPORTED). */
+ * annotation_buffer.cpp:166-181) are on the device, and so is the chain stage of LabeledAligner's coordinate mode (seed chaining,
+ * aligner_labeled.cpp:457-462): mgx_seed_chainer_create / mgx_chain_tables_batch below.  The mode as a whole is not —
+ * mgx_labeled_aligner_create refuses such an annotation (MGX_ERR_UNSUPPORTED). */
 int mgx_annotation_set_coordinates(mgx_annotation *a, uint32_t n_labels, const uint64_t *col_begin, const uint64_t *rows,
                                    const uint64_t *coord_begin, const int64_t *coords);
 /* The same with rows, coord_begin and coords in device memory (col_begin stays a host array); the row-major form is built by
@@ -573,6 +578,65 @@ typedef struct mgx_chain_anchor {
 } mgx_chain_anchor;
 int mgx_chain_seeds(const mgx_config *config, int device, const mgx_chain_anchor *anchors, const uint64_t *list_begin,
                     const uint32_t *query_size, uint64_t n_lists, mgx_chain_anchor *sorted_out, uint32_t *backtrace_out);
+
+/* The chain stage of LabeledAligner's coordinate mode as one device pipeline: the data-parallel half of what the reference does
+ * for a query when its annotation carries k-mer coordinates (dbg_aligner.cpp:545-550, aligner_labeled.cpp:594-721,
+ * aligner_chainer.cpp:341-542).  Reads go in; per (query, strand) the seeds filter_seeds keeps and the finished tables of
+ * chain_seeds come out and stay in device memory for the stage that consumes them.  The sequential half — backtracking the
+ * chains, extend_chain / align_connect, the aggregator — is not built.
+ *
+ * mgx_seed_chainer_create: a handle for that stage.  graph: BASIC mode (the reference has coordinates on BASIC graphs only);
+ * annotation: mgx_annotation_has_coordinates() != 0, on the graph's device, outliving the handle;
+ * config->forward_and_reverse_complement != 0 (the reference chains only where it seeds both strands,
+ * dbg_aligner.cpp:290-297,545-550); config->chain_alignments = 0 as everywhere.  The handle's config is what LabeledAligner's
+ * constructor leaves: DBGAligner's clamps, min / max_seed_length <= k, global_xdrop = 0, chain_alignments = 1
+ * (mgx_aligner_get_config shows it).  Anything else: MGX_ERR_UNSUPPORTED / MGX_ERR_INVALID with the field named in
+ * mgx_last_error.  mgx_labeled_aligner_create keeps refusing such an annotation; on this handle every align / fetch / format call
+ * (mgx_align_batch, mgx_align_batch_device, mgx_fetch_results, mgx_device_results, mgx_decode_results_device,
+ * mgx_fetch_seed_info, mgx_format_*_batch, mgx_gather_start) returns MGX_ERR_UNSUPPORTED.  Destroyed with mgx_aligner_destroy;
+ * options, streams and statistics (mgx_aligner_set_pipeline "seed_lane=..", mgx_aligner_stats: the seeding fields) as on any
+ * aligner.
+ *
+ * mgx_chain_tables_batch, per (query, strand) — list 2q = query q, list 2q + 1 = its reverse complement:
+ *   1. seeding as a label-aware aligner seeds (the same kernels);
+ *   2. filter_seeds with coordinates: every seed gives each label on the row of its first node (rows of dummy nodes are empty)
+ *      the query positions [clipping, clipping + k - offset); labels covering fewer than min_exact_match x |query| positions go;
+ *      a seed keeps the remaining labels of that row with the row's coordinates, each shifted by the seed's offset; seeds left
+ *      without a label go; num_matching = get_num_char_matches_in_seeds of what is left (what the seeder left for a strand
+ *      without seeds);
+ *   3. the kept seeds in reversed order (chain_seeds reverses them; seed_index counts in that order), and per label of a seed one
+ *      anchor per coordinate, at most max_num_seeds_per_locus of them from the largest down: (label, coordinate, clipping,
+ *      clipping + length, chain_score = length, seed_index);
+ *   4. the sort and the DP of mgx_chain_seeds (query_size = |query|, the gap cost tabulated on the host), without its limit of
+ *      6144 anchors per list: lists are bounded by memory alone, a call by 2^31 - 17 (seed, label) pairs and as many anchors
+ *      (more: MGX_ERR_UNSUPPORTED; run the batch in parts).
+ * Every array is sized exactly (a size pass, a scan, a write pass); kernel launches, allocations and synchronising copies per
+ * call do not depend on the number of reads, seeds or labels, and with MGX_CHAIN_TABLES_ON_DEVICE the only device-to-host
+ * traffic is a handful of totals.  The arrays belong to the handle until its next batch call.  A query whose seeding ran out of
+ * a per-read arena has status MGX_ERR_CAPACITY and two empty lists (no retry here; mgx_limits raises the arenas).  n = 0: empty
+ * tables.  seqs / offsets as in mgx_align_batch. */
+int mgx_seed_chainer_create(const mgx_graph *graph, const mgx_config *config, const mgx_limits *limits,
+                            const struct mgx_annotation *annotation, mgx_aligner **out);
+typedef struct mgx_chain_seed { uint32_t clipping, length, offset, n_nodes; uint64_t nodes_begin; } mgx_chain_seed;
+typedef struct mgx_chain_tables {
+    uint64_t n_queries;                 /* list 2q = query q, list 2q + 1 = its reverse complement */
+    const uint64_t *seed_begin;         /* 2n + 1 */
+    const mgx_chain_seed *seeds;        /* the seeds filter_seeds kept, in the order chain_seeds leaves them (reversed) */
+    const uint64_t *nodes;              /* seed s: nodes[nodes_begin .. nodes_begin + n_nodes) */
+    const uint64_t *num_matching;       /* 2n: filter_seeds' return value */
+    const uint64_t *list_begin;         /* 2n + 1 */
+    const mgx_chain_anchor *anchors;    /* sorted as the reference sorts, final chain_score, seed_index relative to seed_begin[list] */
+    const uint32_t *backtrace;          /* relative to list_begin[list]; 0xFFFFFFFF: none */
+    const int32_t *status;              /* n: MGX_OK, or MGX_ERR_CAPACITY from the seeding stage (lists empty; no retry here) */
+} mgx_chain_tables;
+#define MGX_CHAIN_TABLES_ON_DEVICE 1u   /* all arrays stay in device memory (pointers are device pointers), only sizes travel */
+int mgx_chain_tables_batch(mgx_aligner *a, const char *seqs, const uint64_t *offsets, uint64_t n, int seqs_on_device,
+                           uint32_t flags, mgx_chain_tables *out);
+/* the last MGX_CHAIN_TABLES_ON_DEVICE result of the handle copied to host arrays (the handle's, until its next batch call) */
+int mgx_chain_tables_fetch(mgx_aligner *a, mgx_chain_tables *out_host);
+/* test hook, like its siblings: [kernel launches and device-library calls of the chain stage (the seeding stage's are not
+ * counted), device buffers it took or grew, bytes host-to-device, bytes device-to-host] since the library was loaded */
+void mgx_chain_tables_kernel_launch_counts(uint64_t *out4);
 
 /* LabeledAligner<>(graph, config, annotator) (aligner_labeled.hpp:125-127; ctor aligner_labeled.cpp:450-466: DBGAligner's
  * clamps, then min / max_seed_length <= k): an aligner whose batches run label-aware — seeds filtered by label

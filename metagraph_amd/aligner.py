@@ -218,6 +218,15 @@ class Annotation:
     def device_bytes(self):
         return capi.lib().mgx_annotation_device_bytes(self.h)
 
+    def set_coordinates(self, col_begin, rows, coord_begin, coords):
+        """mgx_annotation_set_coordinates on an annotation made by from_sparse(n_rows, col_begin, rows): pair x has the ascending
+        coordinates coords[coord_begin[x] : coord_begin[x + 1]] (host arrays)."""
+        cb, r = np.ascontiguousarray(col_begin, dtype=np.uint64), np.ascontiguousarray(rows, dtype=np.uint64)
+        cob, co = np.ascontiguousarray(coord_begin, dtype=np.uint64), np.ascontiguousarray(coords, dtype=np.int64)
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+        _check(capi.lib().mgx_annotation_set_coordinates(C.c_void_p(self.h.value), C.c_uint32(len(cb) - 1), p(cb), p(r), p(cob),
+                                                         co.ctypes.data_as(C.POINTER(C.c_int64))))
+
     def has_coordinates(self):
         """AnnotationBuffer::has_coordinates: the annotation carries k-mer coordinates"""
         return bool(capi.lib().mgx_annotation_has_coordinates(self.h))
@@ -423,6 +432,85 @@ class Aligner:
         t = capi.Text()
         _check(capi.lib().mgx_format_tsv_batch(self.h, blob, hoff.ctypes.data, arr, len(names), C.byref(t)))
         return _text_of(t, n_headers, "format_tsv_batch: %d headers for a batch of %d queries")
+
+
+class SeedChainer(Aligner):
+    """The chain stage of LabeledAligner's coordinate mode on the GPU (mgx_seed_chainer_create): reads in, per (query, strand) the
+    seeds filter_seeds keeps and the finished tables of chain_seeds out.  graph: BASIC mode; annotation: with k-mer coordinates.
+    Every other batch call of Aligner is refused on such a handle (MGX_ERR_UNSUPPORTED)."""
+
+    def __init__(self, graph, config, annotation, limits=None):
+        self.graph = graph
+        self.annotation = annotation
+        self.h = C.c_void_p()
+        _check(capi.lib().mgx_seed_chainer_create(graph.h, C.byref(config), C.byref(limits) if limits is not None else None,
+                                                  annotation.h, C.byref(self.h)))
+        for opt in Aligner.default_options:
+            self.set_pipeline(opt)
+
+    def chain_tables(self, queries, on_device=False):
+        """mgx_chain_tables_batch -> (arrays, status): arrays = the numpy copies of mgx_chain_tables (seed_begin, seeds, nodes,
+        num_matching, list_begin, anchors, backtrace; chain_lists() splits them per list), status = one code per query.
+        on_device: the tables stay in device memory (MGX_CHAIN_TABLES_ON_DEVICE) and -> the capi.ChainTables of device pointers,
+        not to be dereferenced on the host; fetch_chain_tables() copies them."""
+        blob, offs = pack_queries(queries)
+        t = capi.ChainTables()
+        _check(capi.lib().mgx_chain_tables_batch(self.h, blob, offs.ctypes.data, len(queries), 0,
+                                                 capi.MGX_CHAIN_TABLES_ON_DEVICE if on_device else 0, C.byref(t)))
+        return t if on_device else _chain_tables_of(t)
+
+    def fetch_chain_tables(self):
+        """mgx_chain_tables_fetch: the last on_device result as chain_tables() returns it"""
+        t = capi.ChainTables()
+        _check(capi.lib().mgx_chain_tables_fetch(self.h, C.byref(t)))
+        return _chain_tables_of(t)
+
+
+CHAIN_SEED_DTYPE = np.dtype([("clipping", "<u4"), ("length", "<u4"), ("offset", "<u4"), ("n_nodes", "<u4"), ("nodes_begin", "<u8")])
+CHAIN_ANCHOR_DTYPE = np.dtype([("label", "<u8"), ("coordinate", "<i8"), ("seed_clipping", "<i4"), ("seed_end", "<i4"),
+                               ("chain_score", "<i4"), ("seed_index", "<u4")])
+
+
+def _chain_tables_of(t):
+    """numpy copies of a host mgx_chain_tables -> (dict of arrays, list of status codes)"""
+    n = int(t.n_queries)
+
+    def arr(ptr, count, dtype):
+        if not count:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype, count=count).copy()
+
+    seed_begin, list_begin = arr(t.seed_begin, 2 * n + 1, np.uint64), arr(t.list_begin, 2 * n + 1, np.uint64)
+    seeds = arr(t.seeds, int(seed_begin[-1]), CHAIN_SEED_DTYPE)
+    n_nodes = int(seeds["n_nodes"].sum()) if len(seeds) else 0
+    n_anchors = int(list_begin[-1])
+    out = {"n": n, "seed_begin": seed_begin, "seeds": seeds, "nodes": arr(t.nodes, n_nodes, np.uint64),
+           "num_matching": arr(t.num_matching, 2 * n, np.uint64), "list_begin": list_begin,
+           "anchors": arr(t.anchors, n_anchors, CHAIN_ANCHOR_DTYPE), "backtrace": arr(t.backtrace, n_anchors, np.uint32)}
+    return out, arr(t.status, n, np.int32).tolist()
+
+
+def chain_lists(arrays):
+    """The arrays of SeedChainer.chain_tables per list (list 2q = query q, 2q + 1 = its reverse complement): dicts of
+    seeds [(clipping, length, offset, [nodes])] in chain_seeds' (reversed) order, num_matching,
+    anchors [(label, coordinate, seed_clipping, seed_end, chain_score, seed_index)] and backtrace."""
+    out = []
+    nodes = arrays["nodes"]
+    for l in range(2 * arrays["n"]):
+        sb, se = int(arrays["seed_begin"][l]), int(arrays["seed_begin"][l + 1])
+        lb, le = int(arrays["list_begin"][l]), int(arrays["list_begin"][l + 1])
+        seeds = [(int(s["clipping"]), int(s["length"]), int(s["offset"]),
+                  nodes[int(s["nodes_begin"]):int(s["nodes_begin"]) + int(s["n_nodes"])].tolist()) for s in arrays["seeds"][sb:se]]
+        out.append({"seeds": seeds, "num_matching": int(arrays["num_matching"][l]),
+                    "anchors": [tuple(int(x) for x in a) for a in arrays["anchors"][lb:le].tolist()],
+                    "backtrace": arrays["backtrace"][lb:le].tolist()})
+    return out
+
+
+def chain_tables_kernel_launch_counts():
+    """mgx_chain_tables_kernel_launch_counts -> (kernel launches and device-library calls of the chain stage, device buffers it took
+    or grew, bytes host-to-device, bytes device-to-host) since the library was loaded"""
+    return _four_counts(capi.lib().mgx_chain_tables_kernel_launch_counts)
 
 
 def _text_of(t, n_headers, mismatch):

@@ -98,6 +98,25 @@ class Reads(C.Structure):
                 ("name_offsets", C.POINTER(C.c_uint64))]
 
 
+class ChainAnchor(C.Structure):
+    """mgx_chain_anchor: one (seed, label, coordinate) of a (query, strand), the reference's TableElem"""
+    _fields_ = [("label", C.c_uint64), ("coordinate", C.c_int64), ("seed_clipping", C.c_int32), ("seed_end", C.c_int32),
+                ("chain_score", C.c_int32), ("seed_index", C.c_uint32)]
+
+
+class ChainSeed(C.Structure):
+    _fields_ = [("clipping", C.c_uint32), ("length", C.c_uint32), ("offset", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("nodes_begin", C.c_uint64)]
+
+
+class ChainTables(C.Structure):
+    """mgx_chain_tables (mgx_chain_tables_batch): list 2q = query q, list 2q + 1 = its reverse complement"""
+    _fields_ = [("n_queries", C.c_uint64), ("seed_begin", C.POINTER(C.c_uint64)), ("seeds", C.POINTER(ChainSeed)),
+                ("nodes", C.POINTER(C.c_uint64)), ("num_matching", C.POINTER(C.c_uint64)), ("list_begin", C.POINTER(C.c_uint64)),
+                ("anchors", C.POINTER(ChainAnchor)), ("backtrace", C.POINTER(C.c_uint32)), ("status", C.POINTER(C.c_int32))]
+
+
+MGX_CHAIN_TABLES_ON_DEVICE = 1
 MGX_READS_FASTA, MGX_READS_FASTQ = 1, 2
 MGX_MAP_WANT_NODES = 1
 MGX_MAP_KEEP_NODES = 2
@@ -226,6 +245,11 @@ def lib():
     L.mgx_annotation_destroy.argtypes = [C.c_void_p]
     L.mgx_annotation_create_sparse.argtypes = [C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.mgx_labeled_aligner_create.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Limits), C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mgx_seed_chainer_create.argtypes = [C.c_void_p, C.POINTER(Config), C.POINTER(Limits), C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mgx_chain_tables_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(ChainTables)]
+    L.mgx_chain_tables_fetch.argtypes = [C.c_void_p, C.POINTER(ChainTables)]
+    L.mgx_chain_tables_kernel_launch_counts.argtypes = [C.POINTER(C.c_uint64)]
+    L.mgx_chain_tables_kernel_launch_counts.restype = None
     L.mgx_format_tsv_labeled.argtypes = [C.POINTER(Results), C.c_uint64, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int32,
                                          C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_size_t]
     L.mgx_format_tsv_labeled.restype = C.c_size_t

@@ -191,10 +191,32 @@ enum AlignEvent {
     EV_COUNT
 };
 
+// What a seed-chainer handle (mgx_seed_chainer_create, mgx_chaintab.hip) keeps between calls: the scratch of the chain stage, the
+// tables of its last batch in device memory, and their host copies (mgx_chain_tables_batch without MGX_CHAIN_TABLES_ON_DEVICE,
+// mgx_chain_tables_fetch).  Counts and their exclusive sums: CT_ARRAYS arrays of 2 n + 1 words each.
+struct ChainTabState {
+    enum { CT_PAIRS = 0, CT_SEEDS, CT_NODES, CT_ANCHORS, CT_ARRAYS };
+    DevBuf counts, begins;                                   // per list: (seed, label) pairs seen, kept seeds, their nodes, anchors
+    DevBuf pair_key, pair_key_alt, pair_val, pair_val_alt;   // (label, first covered position) -> end of the covered range, per pair
+    DevBuf kept, n_kept;                                     // per list: the labels at or above the cut-off, ascending
+    DevBuf seeds, nodes, num_matching, status, qsize, penalty;
+    DevBuf anchors, anchors_alt, backtrace, perm, perm_alt, k32, k32_alt, k64, k64_alt, sort_tmp, sort_tmp_anchors;     // (one scratch per sort: what a call allocates does not depend on which sort wants more)
+    std::vector<int32_t> h_penalty;
+    uint64_t n = 0, n_seeds = 0, n_nodes = 0, n_anchors = 0;
+    bool have = false;                                       // the device arrays hold a batch
+    std::vector<uint64_t> h_seed_begin, h_nodes, h_num_matching, h_list_begin;
+    std::vector<mgx_chain_seed> h_seeds;
+    std::vector<mgx_chain_anchor> h_anchors;
+    std::vector<uint32_t> h_backtrace;
+    std::vector<int32_t> h_status;
+};
+
 struct mgx_aligner {
     const mgx_graph *graph = nullptr;
     const mgx_annotation *anno = nullptr;      // label-aware alignment (mgx_labeled_aligner_create)
     bool anno_dummy_clean = false;             // no row of a dummy node holds a label (k_anno_dummy_rows)
+    bool chainer = false;                      // mgx_seed_chainer_create: the handle answers mgx_chain_tables_batch / _fetch only
+    ChainTabState ct;
     mgx_config cfg;
     mgx::DevConfig dcfg;
     mgx_limits user_lim;
@@ -317,6 +339,12 @@ static inline hipError_t copy_sync(mgx_aligner *A, void *dst, const void *src, s
 MGX_INTERNAL int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, const mgx_annotation *anno,
                                 mgx_aligner **out);
 MGX_INTERNAL int collect_stats(mgx_aligner *A, bool mapped, bool aligned);
+// the seeding stage of run_align alone, for a staged and mapped batch: SeedHdr / DevSeed in A->seed_hdr / A->seed_stream (the
+// events collect_stats reads behind the seeding are recorded at its end).  *seeds_wanted: what the seed stream was asked for;
+// more than A->seed_cap: the caller raises A->seed_scale and runs the stage again, as mgx_align_batch_device does
+MGX_INTERNAL int run_seeding(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax, uint64_t *seeds_wanted);
+// every align / fetch / format entry point starts with this: a seed-chainer handle runs none of them
+MGX_INTERNAL int refuse_chainer(const mgx_aligner *A, const char *call);
 // out[0 .. n) = the exclusive sums of in[0 .. n) (device arrays) on the aligner's stream; the scratch is A->scan_tmp
 MGX_INTERNAL int exclusive_sum(mgx_aligner *A, uint64_t *in, uint64_t *out, uint64_t n);
 // The HIP runtime loads a unit's code object onto a device at the first use of one of its kernels.  mgx_graph_create brings those

@@ -133,5 +133,8 @@ int mgx_launch_parse_copy(const void *args, int names, void *stream);
 void mgx_annotation_device_view(const mgx_annotation *a, int *device, uint64_t *n_rows, const uint64_t **head,
                                 const uint32_t **count, const uint32_t **more);
 uint64_t mgx_annotation_uid(const mgx_annotation *a);
+// ... and its row-major k-mer coordinates (mgx_chaintab.hip): the labels of row r are entries row_entry[r] .. row_entry[r + 1) in the
+// order of its label list, entry e has the ascending coordinates coords[coord_off[e] .. coord_off[e + 1])
+void mgx_annotation_coord_view(const mgx_annotation *a, const uint64_t **row_entry, const uint64_t **coord_off, const int64_t **coords);
 
 }  // extern "C"

@@ -187,10 +187,12 @@ void mgx_limits_init_default(mgx_limits *l, uint32_t max_query_length) {
 // ------------------------------------------------------------------------------------------------
 // aligner
 // ------------------------------------------------------------------------------------------------
-int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, const mgx_annotation *anno, mgx_aligner **out) {
+static int aligner_create_for(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, const mgx_annotation *anno, bool chainer,
+                              mgx_aligner **out) {
     if (!g || !config || !out) return fail(MGX_ERR_INVALID, "null argument");
     auto *A = new mgx_aligner();
     std::unique_ptr<mgx_aligner> guard(A);
+    A->chainer = chainer;
     A->graph = g;
     A->anno = anno;
     A->device = g->device;
@@ -202,7 +204,10 @@ int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limit
                        &A->retry_list2, &A->retry_key[0], &A->retry_key[1], &A->lane_scratch, &A->lane_params, &A->lane_bail, &A->lane_hist, &A->seedlane_scratch, &A->seedlane_params,
                        &A->seedlane_bail, &A->seedlane_hist, &A->ms_counts, &A->ms_nodes, &A->ms_sorted, &A->mf_threshold, &A->tf_headers, &A->tf_header_offsets,
                        &A->tf_names, &A->tf_len, &A->tf_begin, &A->tf_text, &A->tf_cap, &A->tf_patch, &A->rd_counts, &A->rd_begins, &A->rd_totals, &A->rd_alns,
-                       &A->rd_nodes, &A->rd_cigar, &A->rd_seqs, &A->rd_status, &A->rd_labels })
+                       &A->rd_nodes, &A->rd_cigar, &A->rd_seqs, &A->rd_status, &A->rd_labels,
+                       &A->ct.counts, &A->ct.begins, &A->ct.pair_key, &A->ct.pair_key_alt, &A->ct.pair_val, &A->ct.pair_val_alt, &A->ct.kept, &A->ct.n_kept,
+                       &A->ct.seeds, &A->ct.nodes, &A->ct.num_matching, &A->ct.status, &A->ct.qsize, &A->ct.penalty, &A->ct.anchors, &A->ct.anchors_alt,
+                       &A->ct.backtrace, &A->ct.perm, &A->ct.perm_alt, &A->ct.k32, &A->ct.k32_alt, &A->ct.k64, &A->ct.k64_alt, &A->ct.sort_tmp, &A->ct.sort_tmp_anchors })
         b->pooled = true;
     {
         std::string err;
@@ -224,7 +229,9 @@ int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limit
         // x-drop off).  Of that mode the device has the annotation (mgx_annotation_get_row_tuples) and the chaining DP
         // (mgx_chain_seeds); the extension between chain seeds (dbg_aligner.cpp:155-250,388-529) is not built: refused, so that
         // the caller keeps the reference's aligner — never answered with the plain label-aware mode
-        if (mgx_annotation_has_coordinates(anno) && g->mode == MGX_MODE_BASIC)
+        // (the chain stage of that mode — seeds, their filter, the anchors and the chainer's tables — is a handle of its own:
+        // mgx_seed_chainer_create)
+        if (!chainer && mgx_annotation_has_coordinates(anno) && g->mode == MGX_MODE_BASIC)
             return fail(MGX_ERR_UNSUPPORTED, "label-aware alignment with coordinates (seed chaining) is not on the device");
         if (arows < g->g.n) return fail(MGX_ERR_INVALID, "the annotation has %llu rows, the graph %llu nodes (row = node - 1)",
                                         (unsigned long long)arows, (unsigned long long)g->g.n);
@@ -250,10 +257,36 @@ int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limit
     return MGX_OK;
 }
 
+int aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, const mgx_annotation *anno, mgx_aligner **out) {
+    return aligner_create_for(g, config, limits, anno, false, out);
+}
+int refuse_chainer(const mgx_aligner *A, const char *call) {
+    return A && A->chainer ? fail(MGX_ERR_UNSUPPORTED, "%s: a seed-chainer handle runs mgx_chain_tables_batch / mgx_chain_tables_fetch only", call) : MGX_OK;
+}
+
 extern "C" {
 
 int mgx_aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, mgx_aligner **out) {
     return aligner_create(g, config, limits, nullptr, out);
+}
+/* The chain stage of LabeledAligner's coordinate mode (include/mgx.h): the handle's config is what LabeledAligner's constructor
+ * leaves for an annotation with coordinates (aligner_labeled.cpp:456-465). */
+int mgx_seed_chainer_create(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, const mgx_annotation *annotation,
+                            mgx_aligner **out) {
+    if (!g || !config || !annotation || !out) return fail(MGX_ERR_INVALID, "null argument");
+    if (g->mode != MGX_MODE_BASIC)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_seed_chainer_create: graph mode %u (the reference has k-mer coordinates on BASIC graphs only)", g->mode);
+    if (!mgx_annotation_has_coordinates(annotation))
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_seed_chainer_create: the annotation has no k-mer coordinates (LabeledAligner chains seeds only with them)");
+    if (!config->forward_and_reverse_complement)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_seed_chainer_create: forward_and_reverse_complement = 0 (the reference chains only where it seeds both strands)");
+    if (config->chain_alignments)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_seed_chainer_create: chain_alignments is set by LabeledAligner itself, never by the caller");
+    mgx_config c = *config;
+    c.global_xdrop = 0;
+    if (int rc = aligner_create_for(g, &c, limits, annotation, true, out)) return rc;
+    (*out)->cfg.chain_alignments = 1;
+    return MGX_OK;
 }
 int mgx_labeled_aligner_create(const mgx_graph *g, const mgx_config *config, const mgx_limits *limits, const mgx_annotation *annotation,
                                mgx_aligner **out) {
@@ -788,7 +821,9 @@ static int extend_multi_pass(mgx_aligner *A, AlignPlan &pl) {
     return MGX_OK;
 }
 
-static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax) {
+// The stages of a batch up to its seeds: limits, the plan, arena and buffers, the parameter block, the two seeders.  lane: plan the
+// lane-per-read extension kernel too (run_align; its scratch is taken before the arena is sized) — a handle that only seeds does not.
+static int seed_stage(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax, bool lane, AlignPlan &pl) {
     {
         std::string err;
         int rc = derive_limits(A->cfg, A->have_user_lim ? &A->user_lim : nullptr, Lmax, &A->lim, &err, A->anno != nullptr, A->label_scale);
@@ -796,11 +831,15 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     }
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, A->graph->device));
-    AlignPlan pl;
     pl.n = n;
     pl.labeled = A->anno != nullptr;
     pl.cus = (uint32_t)prop.multiProcessorCount;
-    if (int rc = plan_lane(A, pl)) return rc;
+    if (lane) {
+        if (int rc = plan_lane(A, pl)) return rc;
+    } else {
+        memset(&pl.LP, 0, sizeof(pl.LP));
+        pl.key_bits = work_key_bits(n);
+    }
     if (int rc = size_arena(A, pl)) return rc;
     if (int rc = size_buffers(A, pl)) return rc;
     fill_params(A, pl, d_seqs, d_offsets);
@@ -811,6 +850,12 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     HIP_TRY(hipEventRecord(A->ev[EV_SEED_LANE_END], A->hstream));
     if (int rc = seed_by_waves(A, pl)) return rc;
     HIP_TRY(hipEventRecord(A->ev[EV_SEEDED], A->hstream));
+    return MGX_OK;
+}
+
+static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax) {
+    AlignPlan pl;
+    if (int rc = seed_stage(A, d_seqs, d_offsets, n, Lmax, true, pl)) return rc;
     A->n_passes = 1;
     A->lane_done = 0;
     A->lane_exact = 0;
@@ -837,6 +882,20 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
         HIP_TRY((hipError_t)launch_extension(A, pl));
     }
     HIP_TRY(hipEventRecord(A->ev[EV_ALIGN_END], A->hstream));
+    return MGX_OK;
+}
+
+// the seeding stage alone (host_state.hpp)
+int run_seeding(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, uint64_t n, uint32_t Lmax, uint64_t *seeds_wanted) {
+    AlignPlan pl;
+    if (int rc = seed_stage(A, d_seqs, d_offsets, n, Lmax, false, pl)) return rc;
+    for (AlignEvent e : { EV_SORTED, EV_LANE_END, EV_ALIGN_END }) HIP_TRY(hipEventRecord(A->ev[e], A->hstream));      // (what collect_stats reads)
+    A->n_passes = 0;
+    A->lane_done = A->lane_exact = A->lane_exact_path = 0;
+    memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
+    unsigned long long wanted = 0;
+    HIP_TRY(copy_sync(A, &wanted, cursor(A, CUR_SEED), 8, hipMemcpyDeviceToHost));
+    *seeds_wanted = wanted;
     return MGX_OK;
 }
 
@@ -961,6 +1020,7 @@ int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
 // kernels only; results stay in HBM
 int mgx_align_batch_device(mgx_aligner *A, const char *seqs, const uint64_t *offsets, uint64_t n, int on_device) {
     if (!A || !seqs || !offsets) return fail(MGX_ERR_INVALID, "null argument");
+    if (int rc = refuse_chainer(A, "mgx_align_batch_device")) return rc;
     if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
     HIP_TRY(hipSetDevice(A->graph->device));
     const char *d_seqs; const uint64_t *d_offsets; uint32_t Lmax;

@@ -387,6 +387,10 @@ void mgx_annotation_device_view(const mgx_annotation *a, int *device, uint64_t *
     *device = a->device; *n_rows = a->n_rows; *head = a->head; *count = a->count; *more = a->more;
 }
 uint64_t mgx_annotation_uid(const mgx_annotation *a) { return a ? a->uid : 0; }
+// the row-major coordinates as the chain stage reads them (mgx_chaintab.hip; library-internal): null without coordinates
+void mgx_annotation_coord_view(const mgx_annotation *a, const uint64_t **row_entry, const uint64_t **coord_off, const int64_t **coords) {
+    *row_entry = a->row_entry; *coord_off = a->coord_off; *coords = a->coords;
+}
 
 /* BinaryMatrix::get_rows(rows) (annotation/binary_matrix/base/binary_matrix.hpp; ColumnMajor: column_major.cpp:27-44) for a
  * whole batch of rows — the ONE call of AnnotationBuffer::fetch_queued_annotations (annotation_buffer.cpp:182) — answered

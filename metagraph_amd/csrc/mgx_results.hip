@@ -125,6 +125,7 @@ static int decode_on_device(mgx_aligner *A, RdWhere where, mgx_results *out, mgx
 
 int mgx_decode_results_device(mgx_aligner *A, mgx_results *out, mgx_results_sizes *sizes) {
     if (!A || !out || !sizes) return fail(MGX_ERR_INVALID, "null argument");
+    if (int rc = refuse_chainer(A, "mgx_decode_results_device")) return rc;
     const uint64_t n = A->n_reads;
     memset(sizes, 0, sizeof(*sizes));
     if (mgx_device_count() <= A->graph->device) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
@@ -151,6 +152,7 @@ int mgx_decode_results_device(mgx_aligner *A, mgx_results *out, mgx_results_size
 
 int mgx_fetch_results(mgx_aligner *A, mgx_results *out) {
     HostStageTimer t_fetch("fetch_results");
+    if (int rc = refuse_chainer(A, "mgx_fetch_results")) return rc;
     const uint64_t n = A->n_reads;
     HIP_TRY(hipSetDevice(A->graph->device));
     // the aligned batch is read back below (post-chaining, the capacity retry): only while the staging buffers still hold it —
@@ -211,6 +213,7 @@ int mgx_fetch_results(mgx_aligner *A, mgx_results *out) {
 int mgx_device_results(mgx_aligner *A, const void **headers, uint64_t *header_bytes, uint64_t *n_queries,
                        const void **stream, uint64_t *stream_words) {
     if (!A) return fail(MGX_ERR_INVALID, "null argument");
+    if (int rc = refuse_chainer(A, "mgx_device_results")) return rc;
     unsigned long long used = 0;
     if (A->n_reads) HIP_TRY(copy_sync(A, &used, cursor(A, CUR_OUT), 8, hipMemcpyDeviceToHost));
     used = std::min<unsigned long long>(used, A->out_words);
@@ -369,6 +372,7 @@ void mgx_aligner_keep_seeds(mgx_aligner *A, int keep) { A->keep_seeds = keep != 
 
 // per read: num_matches fwd/rc, n_seeds fwd/rc, n_extensions, n_columns (6 x u32), and optionally the seeds
 int mgx_fetch_seed_info(mgx_aligner *A, uint32_t *info6, uint32_t *seeds /* [n][2][max_seeds][4] or NULL */, uint32_t *max_seeds_out) {
+    if (int rc = refuse_chainer(A, "mgx_fetch_seed_info")) return rc;
     const uint64_t n = A->n_reads;
     if (A->h_results.size() != n || n == 0) {
         A->h_results.resize(n);

@@ -203,6 +203,7 @@ int mgx_format_tsv_batch(mgx_aligner *A, const char *headers, const uint64_t *he
                          uint32_t n_label_names, mgx_text *out) {
     static_assert(sizeof(TfBatch) == MGX_FORMAT_ARGS_BYTES, "TfBatch differs from what mgx_format.hip takes");
     if (!A || !out || (n_label_names && !label_names)) return fail(MGX_ERR_INVALID, "null argument");
+    if (int rc = refuse_chainer(A, "mgx_format_tsv_batch")) return rc;
     const uint64_t n = A->n_reads;
     if (n && (!headers || !header_offsets)) return fail(MGX_ERR_INVALID, "null argument");
     if (A->cfg.post_chain_alignments)
@@ -269,6 +270,7 @@ int mgx_format_map_batch(mgx_aligner *A, const char *headers, const uint64_t *he
     static_assert(MF_NODES == MGX_MAP_FMT_NODES && MF_COUNT_KMERS == MGX_MAP_FMT_COUNT_KMERS && MF_QUERY_PRESENCE == MGX_MAP_FMT_QUERY_PRESENCE
                   && MF_FILTER_PRESENT == MGX_MAP_FMT_FILTER_PRESENT, "map formats");
     if (!A || !out || !headers || !header_offsets) return fail(MGX_ERR_INVALID, "mgx_format_map_batch: null argument");
+    if (int rc = refuse_chainer(A, "mgx_format_map_batch")) return rc;
     if (format != MGX_MAP_FMT_NODES && format != MGX_MAP_FMT_COUNT_KMERS && format != MGX_MAP_FMT_QUERY_PRESENCE && format != MGX_MAP_FMT_FILTER_PRESENT)
         return fail(MGX_ERR_INVALID, "mgx_format_map_batch: unknown format %d", format);
     if (!A->ms_generation)
@@ -479,6 +481,7 @@ void mgx_format_json_kernel_launch_counts(uint64_t *out4) { for (int x = 0; x < 
 int mgx_format_json_batch(mgx_aligner *A, const char *headers, const uint64_t *header_offsets, uint64_t first, uint64_t n, mgx_text *out) {
     static_assert(sizeof(JfBatch) == MGX_JSONFMT_ARGS_BYTES, "JfBatch differs from what mgx_jsonfmt.hip takes");
     if (!A || !out || (n && (!headers || !header_offsets))) return fail(MGX_ERR_INVALID, "mgx_format_json_batch: null argument");
+    if (int rc = refuse_chainer(A, "mgx_format_json_batch")) return rc;
     if (A->cfg.post_chain_alignments)
         return fail(MGX_ERR_UNSUPPORTED, "mgx_format_json_batch: post_chain_alignments is set and JSON output for chains is not supported");
     const uint64_t n_batch = A->n_reads;
