@@ -28,7 +28,7 @@ extern "C" {
 #define MGX_ABI_VERSION 6      /* still 6: symbols added only: mgx_column_coord_file_read / mgx_column_file_coord_begin / mgx_column_file_coords /
                                 * mgx_annotation_set_coordinates_device / mgx_annotation_load_coord_columns_device / mgx_column_coord_file_decode_device
                                 * (k-mer coordinates read from files, on the host and on the device); before that mgx_annotation_load_columns_device / mgx_column_file_decode_device / mgx_column_decode_kernel_launch_counts
-                                * (`.column.annodbg` files decoded by kernels); before that mgx_stats::n_lane_exact_reads and (later) n_lane_exact_path_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
+                                * (`.column.annodbg` files decoded by kernels); before that mgx_stats::n_lane_exact_reads and (later) n_lane_exact_path_reads, n_lane_exact_sub_reads appended (mgx_aligner_stats fills sizeof(mgx_stats): rebuild callers with this
                                 * header) and the option exact; before that, symbols added only: mgx_decode_results_device / mgx_decode_kernel_launch_counts / the option decode_on_device
                                 * (the mgx_results layout of a batch, written by kernels); before that mgx_format_json_batch / mgx_format_json_kernel_launch_counts (the `align --json` text of a
                                 * batch, written by kernels); before that mgx_format_map_batch / mgx_format_map_kernel_launch_counts / MGX_MAP_KEEP_NODES (the text of
@@ -258,6 +258,10 @@ typedef struct mgx_stats {
                                    class (exact level 2): the first seed starts at the query's first character and ends at a fork or a
                                    merge, every k-mer of the strand is a node; the same closed form over the strand's mapped nodes.
                                    Both counters count label-aware reads too (k_lane_exact_labeled: one label all along) */
+    uint64_t n_lane_exact_sub_reads; /* part of n_lane_reads, none of them in the two counters above: reads finished through the exit's
+                                   substitution class (exact level 3, unlabeled batches; k_lane_exact_sub): the strand's node array has
+                                   one run of zeros behind its first entry, the graph walk across it succeeds, and the result is the
+                                   alignment with one mismatch over the mapped and the walked nodes */
 } mgx_stats;
 enum { MGX_KERNEL_GRP8 = 1, MGX_KERNEL_GRP8_PRIM = 2, MGX_KERNEL_GRP8_ALT = 4, MGX_KERNEL_EXT64 = 8, MGX_KERNEL_LANE = 16,
        MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64, /* the label-aware builds of the 64-lane and the 8-lane kernel */
@@ -421,11 +425,13 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   lane=0|1             the lane-per-read kernel in front of the group kernel (default: automatic).  1 means "where the configuration
  *                        allows it": an aligner with global_xdrop = 0 (per-branch x-drop) never runs it, nor its exact exit below —
  *                        the lane kernels encode the global rule (mgx_stats: n_lane_reads and both exact counters stay 0)
- *   exact=0|1|2          the lane kernel's exact exit: reads whose result is known when seeding ends are finished in closed form,
+ *   exact=0|1|2|3        the lane kernel's exact exit: reads whose result is known when seeding ends are finished in closed form,
  *                        without DP.  1: reads whose first seed spans the query; 2: also reads whose first seed starts at the query's
- *                        first character and whose every k-mer is a node (perfect reads that cross a fork or a merge).  Default:
- *                        automatic — level 2 for the batches the lane kernel takes of its own accord; 1 / 2: wherever the lane
- *                        kernel runs and the configuration allows it.  Label-aware batches (wherever the lane kernel takes them:
+ *                        first character and whose every k-mer is a node (perfect reads that cross a fork or a merge); 3: also reads
+ *                        with one substitution behind their first k characters, where the graph walk across it succeeds (unlabeled
+ *                        batches whose scores make that alignment the strict optimum; elsewhere 3 means 2).  Default:
+ *                        automatic — level 3 (label-aware batches: 2) for the batches the lane kernel takes of its own accord;
+ *                        1 / 2 / 3: wherever the lane kernel runs and the configuration allows it.  Label-aware batches (wherever the lane kernel takes them:
  *                        no dummy node's row holds a label) are included, at either level and in the automatic default: there
  *                        the exit takes the reads that keep one label all along — the label filter leaves the seeds one label L
  *                        and every node of the path has the row { L } — and the label list of the alignment is [L]; with one

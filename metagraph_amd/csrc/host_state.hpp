@@ -234,6 +234,7 @@ struct mgx_aligner {
     uint64_t lane_done = 0;
     uint64_t lane_exact = 0;      // ... of them through the exact exit (k_lane_exact) with a first seed that spans the query
     uint64_t lane_exact_path = 0; // ... and through its path class (level 2: every k-mer a node, the first seed shorter)
+    uint64_t lane_exact_sub = 0;  // ... and through its substitution class (level 3: one run of zeros, walked; counted in neither of the two above)
     unsigned long long lane_hist_h[32] = { 0 };
     DevBuf seedlane_scratch, seedlane_params, seedlane_bail, seedlane_hist;   // lane-per-read seeder: seed buffers, parameter block, the reads it leaves, why
     uint64_t seedlane_launched = 0;    // the last batch ran it (its counters are read back by collect_stats)

@@ -11,7 +11,7 @@
 // its own, so the struct types differ by name from unit to unit).  The blocks are the same plain data everywhere: each unit
 // asserts the size of its own instantiation against these, next to the cast.
 constexpr size_t MGX_ALIGN_PARAMS_BYTES = 728;          // sizeof(AlignParams), align_types.hpp
-constexpr size_t MGX_LANE_PARAMS_BYTES = 856;           // sizeof(LaneParams), lane_types.hpp
+constexpr size_t MGX_LANE_PARAMS_BYTES = 864;          // sizeof(LaneParams), lane_types.hpp
 constexpr size_t MGX_SEED_LANE_PARAMS_BYTES = 824;      // sizeof(SeedLaneParams), seed_lane.hpp
 constexpr size_t MGX_DEV_GRAPH_BYTES = 160;             // sizeof(DevGraph), dev_graph.hpp
 constexpr size_t MGX_FORMAT_ARGS_BYTES = 128;           // sizeof(TfBatch), tsv_format.hpp
@@ -77,6 +77,7 @@ int mgx_seed_load(void);
 // mgx_lane.hip: the lane-per-read kernel.  d_params: LaneParams in DEVICE memory; blocks = resident wavefronts
 int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream);
 int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, int labeled, void *stream);    // k_lane_exact / k_lane_exact_labeled, before the work sort when LaneParams::exact
+int mgx_launch_lane_exact_sub(const void *d_params, uint32_t blocks, void *stream);             // k_lane_exact_sub, behind k_lane_exact when LaneParams::exact >= 3
 int mgx_lane_waves_per_simd(void);
 
 // mgx_seedlane.hip: the lane-per-read seeder.  d_params: SeedLaneParams in DEVICE memory; long_reads: the build for reads of

@@ -1411,7 +1411,12 @@ MGX_DEV int lane_read_dp(const LaneParams &LP, uint64_t read, const uint32_t ite
 // to the query's end exactly as inside a seed, every side branch carries a mismatch or a gap and ends below the full score, and
 // the later seeds, whose last nodes lie on this path with the full prefix score, are found dead by check_seed.  Same score, same
 // CIGAR; the nodes are the strand's mapped nodes, which is where LANE_EMIT_EXACT takes them from anyway.
-enum { LANE_EXACT_NONE = 0, LANE_EXACT_SPAN = 1, LANE_EXACT_PATH = 2 };
+//
+// The substitution class (LaneParams::exact >= 3, unlabeled batches): the header tests hold, and the strand's node array has exactly
+// one run of zeros [lo, hi], lo >= 1, of k entries (or reaching the array's end) — the k-mers that cover one query position
+// p = lo + k - 1.  lane_exact_class() returns LANE_EXACT_SUB for such a CANDIDATE without filling anything; lane_exact_sub() walks
+// the graph across the run and decides (the conditions and why they carry the closed form: there and DESIGN.md 3.4).
+enum { LANE_EXACT_NONE = 0, LANE_EXACT_SPAN = 1, LANE_EXACT_PATH = 2, LANE_EXACT_SUB = 3 };
 
 // whether none of the n node indices at p is 0 (a k-mer that is not in the graph), with the widest loads p's alignment allows:
 // single words up to the first 16-byte boundary, four nodes to a load from there on, single words for the rest
@@ -1426,6 +1431,38 @@ MGX_DEV bool lane_all_nodes(const uint32_t *p, const int32_t n) {
     }
     for (; x < n; ++x)
         if (!gld(p + x)) return false;
+    return true;
+}
+
+// the one run of zeros among the n node indices at p, with the loads of lane_all_nodes(): false at the first zero behind a run
+// that has ended (a second run); else true with the run in [lo, hi], lo == -1 if there is no zero at all
+struct LaneZeroRun { int32_t a, b; bool ok; };
+MGX_DEV LaneZeroRun lane_zero_run_word(LaneZeroRun r, const uint32_t v, const int32_t x) {
+    if (v) return r;
+    if (r.a < 0) { r.a = x; r.b = x; }
+    else if (r.b == x - 1) r.b = x;
+    else r.ok = false;
+    return r;
+}
+MGX_DEV bool lane_one_zero_run(const uint32_t *p, const int32_t n, int32_t &lo, int32_t &hi) {
+    LaneZeroRun r = { -1, -1, true };
+    int32_t x = 0;
+    for (; x < n && ((uintptr_t)(p + x) & 15u); ++x) {
+        r = lane_zero_run_word(r, gld(p + x), x);
+        if (!r.ok) return false;
+    }
+    for (; x + 4 <= n; x += 4) {
+        const LaneNodeQuad q = gld((const LaneNodeQuad *)(p + x));
+        if (q.v[0] && q.v[1] && q.v[2] && q.v[3]) continue;
+        r = lane_zero_run_word(r, q.v[0], x); r = lane_zero_run_word(r, q.v[1], x + 1);
+        r = lane_zero_run_word(r, q.v[2], x + 2); r = lane_zero_run_word(r, q.v[3], x + 3);
+        if (!r.ok) return false;
+    }
+    for (; x < n; ++x) {
+        r = lane_zero_run_word(r, gld(p + x), x);
+        if (!r.ok) return false;
+    }
+    lo = r.a; hi = r.b;
     return true;
 }
 
@@ -1516,8 +1553,10 @@ MGX_DEV bool lane_all_rows(const AlignParams &P, const uint32_t *p, const int32_
 // that passed them all and whose first seed ends short of the query, and the rows along the path (label-aware) last of all.
 // LABELED: whether the batch may be label-aware (k_lane_exact, the kernel of the unlabeled batches, is compiled without that half:
 // its code is what it was); a label-aware batch under LABELED = false is refused.
+// run_lo / run_hi (level 3, unlabeled): for LANE_EXACT_SUB the run of zeros of a candidate of the substitution class.
 template <bool LABELED>
-MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t *L_out, int *strand, uint32_t hdr4[4], uint32_t *label_out) {
+MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t *L_out, int *strand, uint32_t hdr4[4], uint32_t *label_out,
+                             int32_t &run_lo, int32_t &run_hi) {
     const AlignParams &P = LP.P;
     const DevConfig &cfg = P.cfg;
     // (label-aware: only where no dummy node's row holds a label — the condition under which the lane reads rows at all; nothing
@@ -1566,7 +1605,20 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
     if (full < cfg.min_path_score || full < cfg.min_cell_score) return LANE_EXACT_NONE;
     const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
     const int32_t nk = L - k + 1;
-    if (len != L) {
+    int cls = len == L ? LANE_EXACT_SPAN : LANE_EXACT_PATH;
+    if (!LABELED && len != L && LP.exact >= 3u) {
+        // level 3: one scan tells the path class (no zero) from a candidate of the substitution class (one run of zeros behind
+        // index 0: k entries, or up to k that reach the array's end — a longer run there covers a second mismatch) from the rest
+        int32_t lo = -1, hi = -1;
+        if (!lane_one_zero_run(rn, nk, lo, hi)) return LANE_EXACT_NONE;
+        if (lo >= 0) {
+            const int32_t len_run = hi - lo + 1;
+            if (lo < 1 || len_run > k || (hi != nk - 1 && len_run != k)) return LANE_EXACT_NONE;
+            run_lo = lo; run_hi = hi;
+            cls = LANE_EXACT_SUB;
+        }
+    }
+    if ((LABELED || LP.exact < 3u) && len != L) {
         // the path class.  The k-mer behind the seed's last one first: where the seed ended at a character the graph does not
         // have — most reads that come this far and are not in the class — that one word settles it
         const int32_t next = len - k + 1;
@@ -1578,18 +1630,21 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
     if (labeled && !lane_all_rows(P, rn, nk, label)) return LANE_EXACT_NONE;
     *L_out = L; *strand = s; *label_out = label;
     hdr4[0] = nm0; hdr4[1] = nm1; hdr4[2] = (uint32_t)ns0; hdr4[3] = (uint32_t)ns1;
-    return len == L ? LANE_EXACT_SPAN : LANE_EXACT_PATH;
+    return cls;
 }
 
 // Returns the class if R is filled (as lane_read_dp() fills it for LR_DONE; no extension ran: n_extensions = n_columns = 0),
 // else LANE_EXACT_NONE.  The closed form is the same for both classes; label-aware it carries the read's one label behind it.
+// LANE_EXACT_SUB: a candidate of the substitution class — nothing filled but R.strand and the run of zeros: the caller
+// lists it for k_lane_exact_sub (mgx_lane.hip) or, in the host model, calls lane_exact_sub() (below).
 template <bool LABELED>
-MGX_DEV int lane_exact_t(const LaneParams &LP, const uint64_t read, LaneResult &R) {
+MGX_DEV int lane_exact_t(const LaneParams &LP, const uint64_t read, LaneResult &R, int32_t &run_lo, int32_t &run_hi) {
     int32_t L = 0;
     int s = 0;
     uint32_t h[4], label = 0;
-    const int cls = lane_exact_class<LABELED>(LP, read, &L, &s, h, &label);
+    const int cls = lane_exact_class<LABELED>(LP, read, &L, &s, h, &label, run_lo, run_hi);
     if (cls == LANE_EXACT_NONE) return cls;
+    if (cls == LANE_EXACT_SUB) { R.strand = s; return cls; }
     const int32_t k = (int32_t)LP.P.g.k;
     ReadResult &rr = R.rr;
     rr.status = ST_OK; rr.n_alignments = 0; rr.score = 0; rr.offset = 0; rr.n_nodes = rr.n_cigar = rr.seq_len = 0;
@@ -1602,15 +1657,179 @@ MGX_DEV int lane_exact_t(const LaneParams &LP, const uint64_t read, LaneResult &
     R.words = (uint32_t)R.n_nodes + 1u + ((uint32_t)L + 3) / 4 + ((LABELED && LP.P.labeled) ? 2u : 0u);
     return cls;
 }
+// ---- the substitution class (level 3; DESIGN.md 3.4 "the substitution class") ----
+// One step of the walk: the child of node v whose character code is c, else 0 — fwd() to the target's last edge, then pick_edge
+// among that node's edges (dev_graph.hpp), the edge dropped if the graph's mask does.  (An edge per label and node: the same child
+// outgoing() reports for c.)
+MGX_DEV uint32_t lane_sub_step(const DevGraph &g, const uint32_t vv, const uint32_t c, LineCtr &lc) {
+    const uint64_t v = vv;
+    ++lc.rank_lines;
+    const Block cur = load_block(g, (uint32_t)(v >> 6));
+    const uint32_t w = block_W(cur, (int)(v & 63));
+    if (v > 1 && w == 0) return 0;
+    Block tgt;
+    const uint64_t lst = fwd_from(g, v, cur, w % SIGMA, tgt, lc);
+    if (!lst) return 0;
+    const uint64_t e = pick_edge_from(g, lst, tgt, c, lc);
+    return (e >= 2 && in_graph(g, e)) ? (uint32_t)e : 0u;
+}
+// the number of children of v (dev_graph.hpp outgoing(): sentinel children dropped); *first / *first_code: the first one
+MGX_DEV int lane_sub_children(const DevGraph &g, const uint32_t v, uint32_t *first, uint32_t *first_code, LineCtr &lc) {
+    uint64_t nodes[4] = { 0, 0, 0, 0 };
+    uint32_t codes[4] = { 0, 0, 0, 0 };
+    const int n = outgoing(g, v, nodes, codes, lc);
+    *first = (uint32_t)nodes[0]; *first_code = codes[0];
+    return n;
+}
+
+// A candidate (read, strand s, run of zeros [lo, hi] in the strand's node array: lane_exact_class() returned LANE_EXACT_SUB) ->
+// whether the read is in the substitution class; then R is filled as lane_exact_t() fills it, with the CIGAR "p= 1X (L-1-p)=",
+// R.j_hi = p and R.label = the graph's character code at p (neither has another meaning under LANE_EMIT_EXACT in an unlabeled
+// batch; R.n_runs > 1 tells lane_emit_t() that this is such a read), and walk[x * wstride] holds node lo + x of the path for
+// x <= hi - lo (LANE_SUB_MAX_WALK words at most: on the device LDS, in the host model the lane's cold words).  Nothing is written
+// outside walk[] and R: a read that fails any test runs the DP as if nothing had happened.
+//
+// With p = lo + k - 1 the query position every k-mer of the run covers, v = the node in front of the run (the k-mer that ends at
+// p - 1), m the match score and mm = score(g, strand[p]):
+//  1. v has exactly one child; its character g differs from strand[p] (a node with two children: the extender would park one of
+//     them with a score equal to the head's where both are mismatches — out).
+//  2. From that child the child spelled by strand[j] exists for j = p + 1 .. hi + k - 1 (forks allowed: children of a node differ in
+//     their last character, so the walk is the only path that spells g + strand[p + 1 ..]); interior run: the node reached after k
+//     steps has the array's next entry as its child by strand[p + k].  An insertion in the read leaves k zeros too; its walk fails
+//     (or succeeds where the substitution is an alignment as well, which then scores higher: gap_opening + m < mm).
+//  2a. A run SHORTER than k (it reaches the array's end, p > L - k): every k-mer that covers p also covers the positions L - k .. p - 1,
+//     so a path that leaves at a fork there, takes the other allele's character at j and then spells strand[j + 1 ..], strand[p]
+//     included, is a second alignment with one mismatch — the read that recombines two SNPs less than k apart — which ties with or
+//     beats the one at p.  Tested here: none of the path's nodes that end at L - k - 1 .. p - 2 (array indices L - 2k .. lo - 2) has
+//     a second child.  (A run of k entries, interior or at the end, needs no such test: see 3.)
+//  3. The optimum is strict.  No path from the first node spells the strand (its k-mers at [lo, hi] are not nodes); one with one
+//     mismatch at j != p leaves a k-mer that covers p and not j spelled out, a node — such a k-mer exists for every j when the run has
+//     k entries, and for every j outside L - k .. p - 1 when it has fewer, where 2a rules the path out — so it has it at p and is the walk; two mismatches,
+//     or any gap, score below (lane_exact_sub_config()).  An alignment that stops short of the query's end loses m per character
+//     and right_end_bonus >= 0; one that stops in front of p scores m p + left_end_bonus: mm + m (L - 1 - p) + right_end_bonus > 0
+//     is tested here.
+//  4. extend() finds it.  The head column — one node of the path per query character — is the strict top of the queue up to p as in
+//     the path class; its child at p holds m p + left_end_bonus + mm (the deletion cell beside it less: gap_opening < mm), above
+//     every child parked at a fork in front of p (at most m (p - 1) + left_end_bonus + the largest mismatch score; hi - lo < m) and
+//     not under the x-drop (lo + xdrop >= 0); from there on it gains m per column while a parked child gains nothing.  While the
+//     head's maximum is below the best score so far, m p + left_end_bonus, extend() DOES test its early stops
+//     (aligner_extender_methods.cpp:521-547) and the extension cut-off (:660-672):
+//      - a popped column makes at most four children and only columns of the path have been popped, so the table holds at most
+//        4 L + 1 columns: (4 L + 1) / L < max_nodes_per_seq_char is tested here;
+//      - a column takes 136 bytes (doubling: 272) and three vectors of at most L + 1 cells (doubling: 24 (L + 1) bytes):
+//        (4 L + 1) (272 + 24 (L + 1)) bytes <= max_ram_per_alignment is tested here;
+//      - has_extension: cell + the matches left >= (score_t)(best x rel_score_cutoff), i.e. m (L - 1) + left_end_bonus + mm against
+//        the cut-off of best = m p + left_end_bonus, computed as the reference does: tested here.
+//  5. The later seeds are dead: each one's last node is the path's node at its last query position lpos (a seed with offset 0
+//     takes its nodes from the array, outside the run; one with an offset carries its node: compared) and the path's prefix score
+//     there, m (lpos + 1) + left_end_bonus (+ mm - m from p on), is not below the seed's own m length (+ left_end_bonus at clipping 0).
+//  6. The class score passes min_path_score and min_cell_score.
+MGX_DEV bool lane_exact_sub(const LaneParams &LP, const uint64_t read, const int s, const int32_t lo, const int32_t hi,
+                            uint32_t *walk, const int32_t wstride, LaneResult &R, LineCtr &lc) {
+    const AlignParams &P = LP.P;
+    const DevConfig &cfg = P.cfg;
+    const int32_t k = (int32_t)P.g.k, m = LP.self_score;
+    const uint64_t off = gld(P.offsets + read);
+    const int32_t L = (int32_t)(gld(P.offsets + read + 1) - off);
+    const int32_t nk = L - k + 1, p = lo + k - 1;
+    if (lo < 1 || hi < lo || hi >= nk || hi - lo + 1 > k || hi - lo + 1 > LANE_SUB_MAX_WALK) return false;
+    const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
+    const uint64_t wb = packed_word_begin(off, read);
+    const uint64_t *pw = LP.pk[s] + wb;
+    // (a character outside ACGT is not for the lane at all: hand-over code 5 of lane_read_dp())
+    for (int32_t j = 0; j < (L + 31) >> 5; ++j)
+        if (gld(LP.iv[s] + wb + j)) return false;
+    auto qcode = [&](const int32_t j) -> uint32_t { return ((uint32_t)(gld(pw + (j >> 5)) >> (2 * (j & 31))) & 3u) + 1u; };
+    // 1. the one child of the node in front of the run
+    uint32_t g_node = 0, g = 0;
+    const uint32_t qp = qcode(p);
+    if (lane_sub_children(P.g, gld(rn + lo - 1), &g_node, &g, lc) != 1 || g == qp) return false;
+    const int32_t mm = (int32_t)(int8_t)(LP.t4[g - 1] >> (8 * (qp - 1)));
+    // 3., 4., 6.: what needs no graph first
+    const int32_t lb = cfg.left_end_bonus, rb = cfg.right_end_bonus;
+    const int32_t core = m * (L - 1) + mm + lb, score = core + rb;
+    if (score < cfg.min_path_score || score < cfg.min_cell_score) return false;
+    if (!(mm + m * (L - 1 - p) + rb > 0)) return false;
+    if (!((double)(4 * L + 1) / (double)L < cfg.max_nodes_per_seq_char)) return false;
+    if (!((double)(4 * L + 1) * (double)(272 + 24 * (L + 1)) / 1'000'000 <= cfg.max_ram_per_alignment)) return false;
+    if (core < (int32_t)((double)(m * p + lb) * cfg.rel_score_cutoff)) return false;      // (partial_sum_offset is 0: an fma with 0 is the product)
+    // 2. the walk
+    uint32_t cur = g_node;
+    walk[0] = cur;
+    for (int32_t x = 1; x <= hi - lo; ++x) {
+        const uint32_t nx = lane_sub_step(P.g, cur, qcode(p + x), lc);
+        if (!nx) return false;
+        cur = nx;
+        walk[x * wstride] = cur;
+    }
+    if (hi < nk - 1) {
+        const uint32_t nx = lane_sub_step(P.g, cur, qcode(p + k), lc);
+        if (!nx || nx != gld(rn + hi + 1)) return false;
+    }
+    // 2a. a run shorter than k (it reaches the array's end): no fork in front of the mismatch inside the last k characters
+    for (int32_t x = imax(L - 2 * k, 0); x <= lo - 2; ++x) {
+        uint32_t f = 0, fc = 0;
+        if (lane_sub_children(P.g, gld(rn + x), &f, &fc, lc) != 1) return false;
+    }
+    // 5. the later seeds
+    const SeedHdr *hp = P.seed_hdr + read;
+    const int32_t ns0 = (int32_t)gld(&hp->n_seeds[0]), ns1 = (int32_t)gld(&hp->n_seeds[1]);
+    const DevSeed *seeds = P.seed_stream + gld(&hp->off) + (s ? ns0 : 0);
+    const int32_t n = s ? ns1 : ns0;
+    for (int32_t t = 1; t < n; ++t) {
+        const DevSeed *sj = seeds + t;
+        const int32_t cl = (int32_t)gld(&sj->clipping), len = (int32_t)gld(&sj->length), so = (int32_t)gld(&sj->offset);
+        const int32_t lpos = len + cl - 1;
+        const int32_t lscore = len * m + (!cl ? lb : 0) + (!(L - cl - len) ? rb : 0);
+        const int32_t prefix = m * (lpos + 1) + lb + (lpos >= p ? mm - m : 0) + (lpos == L - 1 ? rb : 0);
+        if (lpos < 0 || lpos >= L || prefix < lscore) return false;
+        if (so) {
+            const int32_t x = lpos - k + 1;
+            if (x < 0) return false;
+            const uint32_t on_path = (x >= lo && x <= hi) ? walk[(x - lo) * wstride] : gld(rn + x);
+            if (gld(&sj->node) != on_path) return false;
+        }
+    }
+    // the closed form
+    ReadResult &rr = R.rr;
+    rr.status = ST_OK; rr.n_alignments = 0; rr.score = 0; rr.offset = 0; rr.n_nodes = rr.n_cigar = rr.seq_len = 0;
+    rr.orientation = 0; rr.stream_off = 0;
+    rr.num_matches_fwd = gld(&hp->num_matching[0]); rr.num_matches_rc = gld(&hp->num_matching[1]);
+    rr.n_seeds_fwd = (uint32_t)ns0; rr.n_seeds_rc = (uint32_t)ns1;
+    rr.n_extensions = 0; rr.n_columns = 0;
+    R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0; R.label = g;
+    R.score = score;
+    R.offset = 0; R.clip = 0; R.end_clip = 0; R.n_runs = p == L - 1 ? 2 : 3; R.j_hi = p; R.n_nodes = nk; R.n_seq = L;
+    R.words = (uint32_t)R.n_nodes + (uint32_t)R.n_runs + ((uint32_t)L + 3) / 4;
+    return true;
+}
+static_assert(LANE_COLD_WORDS >= LANE_SUB_MAX_WALK, "the host model keeps a walk in the lane's cold words");
+
+// (the host model's form: a candidate of the substitution class is walked at once, the path's nodes in the lane's cold words —
+// lane_read_dp() has not run for this read — and the walk's graph lines in the lane's record, where lane_read_dp() counts its own)
+MGX_DEV int lane_exact_walked(const LaneParams &LP, const uint64_t read, LaneResult &R, uint8_t *scratch, const LaneChip &chip) {
+    int32_t run_lo = 0, run_hi = 0;
+    const int cls = LP.P.labeled ? lane_exact_t<true>(LP, read, R, run_lo, run_hi) : lane_exact_t<false>(LP, read, R, run_lo, run_hi);
+    if (cls != LANE_EXACT_SUB) return cls;
+    if (!scratch || !chip.cold) return LANE_EXACT_NONE;
+    LineCtr lc = { 0, 0, 0 };
+    const bool ok = lane_exact_sub(LP, read, R.strand, run_lo, run_hi, chip.cold, chip.cstride, R, lc);
+    uint32_t *rec = lane_record(LP, scratch, chip.lane);
+    gst(rec + 27, gld(rec + 27) + lc.rank_lines + lc.bit_lines); gst(rec + 28, gld(rec + 28) + lc.select_lines);
+    return ok ? LANE_EXACT_SUB : LANE_EXACT_NONE;
+}
+// the two classes that need no walk (a candidate of the substitution class: LANE_EXACT_NONE here)
 MGX_DEV int lane_exact(const LaneParams &LP, const uint64_t read, LaneResult &R) {
-    return LP.P.labeled ? lane_exact_t<true>(LP, read, R) : lane_exact_t<false>(LP, read, R);
+    int32_t run_lo = 0, run_hi = 0;
+    const int cls = LP.P.labeled ? lane_exact_t<true>(LP, read, R, run_lo, run_hi) : lane_exact_t<false>(LP, read, R, run_lo, run_hi);
+    return cls == LANE_EXACT_SUB ? LANE_EXACT_NONE : cls;
 }
 
 // One read, as the host model calls it: the exact exit where it is on, else the DP.  (On the device the two are two kernels,
 // mgx_lane.hip: k_lane_exact runs lane_exact() on every read before the work sort, k_lane runs lane_read_dp() on the others.)
 MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, const int pass, uint8_t *scratch, const LaneChip &chip,
                       LaneCounters &ctr, LaneResult &R) {
-    if (!pass && LP.exact && lane_exact(LP, read, R) != LANE_EXACT_NONE) return LR_DONE;
+    if (!pass && LP.exact && lane_exact_walked(LP, read, R, scratch, chip) != LANE_EXACT_NONE) return LR_DONE;
     return lane_read_dp(LP, read, item, pass, scratch, chip, ctr, R);
 }
 
@@ -1618,7 +1837,8 @@ MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, 
 // atomic per wavefront on the device), the result record, the seed dump of the test hook
 // WITH_EXACT: R may be what lane_exact() left (the kernel writes those reads apart, and keeps the closed form's code out of the
 // path behind the DP: k_lane has no register to spare, mgx_lane.hip)
-template <bool WITH_EXACT>
+// WITH_SUB: ... or what lane_exact_sub() left (k_lane_exact_sub and the host model only: the other kernels keep their code)
+template <bool WITH_EXACT, bool WITH_SUB = false>
 MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
                          const uint64_t so) {
     const AlignParams &P = LP.P;
@@ -1651,15 +1871,25 @@ MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_
                 const uint64_t off = gld(P.offsets + read);
                 const uint32_t *rn = (R.strand ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
                 const uint64_t *pw = LP.pk[R.strand] + packed_word_begin(off, read);
-                for (int32_t x = 0; x < R.n_nodes; ++x) gst(dst + x, gld(rn + x));
-                gst(dst + R.n_nodes + nc++, ((uint32_t)R.n_seq << 3) | OP_MATCH);
+                // (the substitution class, R.n_runs > 1: "p= 1X (L-1-p)=" with p = R.j_hi, the walked nodes from chip.cold in place of
+                // the run of zeros that begins at p - k + 1, the graph's character R.label at p: lane_exact_sub())
+                const bool sub = WITH_SUB && R.n_runs > 1;
+                const int32_t sp = sub ? R.j_hi : -1, lo = sub ? sp - k_minus_1 : R.n_nodes;
+                for (int32_t x = 0; x < R.n_nodes; ++x) gst(dst + x, (x >= lo && x <= sp) ? chip.cold[(x - lo) * chip.cstride] : gld(rn + x));
+                if (sub) {
+                    gst(dst + R.n_nodes + nc++, ((uint32_t)sp << 3) | OP_MATCH);
+                    gst(dst + R.n_nodes + nc++, (1u << 3) | OP_MISMATCH);
+                    if (R.n_runs > 2) gst(dst + R.n_nodes + nc++, ((uint32_t)(R.n_seq - 1 - sp) << 3) | OP_MATCH);
+                } else {
+                    gst(dst + R.n_nodes + nc++, ((uint32_t)R.n_seq << 3) | OP_MATCH);
+                }
                 uint32_t *dw = dst + R.n_nodes + n_cigar;
                 uint64_t qw = 0;
                 for (int32_t x = 0; x < R.n_seq; x += 4) {
                     if (!(x & 31)) qw = gld(pw + (x >> 5));
                     uint32_t v = 0;
                     for (int t = 0; t < 4; ++t)
-                        if (x + t < R.n_seq) v |= (uint32_t)decode_code(((uint32_t)(qw >> (2 * ((x + t) & 31))) & 3u) + 1u) << (8 * t);
+                        if (x + t < R.n_seq) v |= (uint32_t)decode_code(x + t == sp ? R.label : ((uint32_t)(qw >> (2 * ((x + t) & 31))) & 3u) + 1u) << (8 * t);
                     gst(dw + (x >> 2), v);
                 }
             } else if (R.mode == LANE_EMIT_ARRAYS) {
@@ -1722,7 +1952,7 @@ MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_
 
 MGX_DEV void lane_emit(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
                        const uint64_t so) {
-    lane_emit_t<true>(LP, read, scratch, chip, R, so);
+    lane_emit_t<true, true>(LP, read, scratch, chip, R, so);
 }
 
 } // namespace mgx

@@ -58,17 +58,28 @@ struct LaneParams {
     unsigned long long *bail_hist;       // [32] reads passed on, by the LANE_BAIL code of the test that sent them (lane_read.hpp);
                                          // [LANE_HIST_EXACT] reads finished through the exact exit (part of *done_count, which is
                                          // what the host reads; the word is there for probes of a launch's counters);
-                                         // [LANE_HIST_EXACT_PATH] those of them without a spanning first seed (the path class)
+                                         // [LANE_HIST_EXACT_PATH] those of them without a spanning first seed (the path class);
+                                         // [LANE_HIST_EXACT_SUB] those of them k_lane_exact_sub finished (the substitution class);
+                                         // [LANE_HIST_SUB_CAND] the entries of sub_list
     // (behind what k_lane reads, whose offsets stay what they were)
     uint32_t exact;                      // the level of the exact exit (lane_read.hpp; only where lane_exact_config() holds).  1: a read whose
                                          // first seed spans the query is finished without DP; 2: also a read whose first seed starts at
-                                         // the query's first character and whose every k-mer is a node (the path class).  0 by default:
-                                         // every read runs its columns
+                                         // the query's first character and whose every k-mer is a node (the path class); 3: also a read
+                                         // with one substitution behind its first k characters (the substitution class: unlabeled batches
+                                         // under lane_exact_sub_config() only, label-aware ones stay at 2).  0 by default: every read
+                                         // runs its columns
     uint32_t done_key;                   // exact, on the device: the work key k_lane_exact gives the reads it finished — above every
                                          // key of the seeding phase, so that the work sort puts them behind the items k_lane is launched on
+    struct LaneSubCand *sub_list;        // exact >= 3: the reads that passed the header tests and have one run of zeros in their node
+                                         // array, listed by k_lane_exact for k_lane_exact_sub (bail_hist[LANE_HIST_SUB_CAND] of them)
 };
+// a candidate of the substitution class: the read, the strand aligned, the run of zeros [lo, hi] in that strand's node array
+struct alignas(16) LaneSubCand { uint32_t read, strand, lo, hi; };
 constexpr int LANE_HIST_EXACT = 48;        // (bail_hist has 64 words; [32 .. 41] are the section timers of -DMGX_LANE_TIMERS builds)
 constexpr int LANE_HIST_EXACT_PATH = 49;
+constexpr int LANE_HIST_EXACT_SUB = 50;
+constexpr int LANE_HIST_SUB_CAND = 51;
+constexpr int LANE_SUB_MAX_WALK = 32;      // nodes a walk across a substitution makes at most: k <= 32 (lane_enabled)
 
 // columns of an extension along one path: the root, one per query character, the deletions past the query's end that the x-drop
 // still allows, the spare slot of the `size >= capacity - 1` test (a read that needs more goes to the group kernel)
@@ -121,10 +132,44 @@ inline bool lane_exact_config(const mgx_config &c, const DevConfig &d, uint32_t 
     return true;
 }
 
+// Whether level 3 of the exact exit (the substitution class, lane_read.hpp lane_exact_sub()) may be on, given lane_exact_config():
+// unlabeled batches only, and the conditions that make the alignment with one mismatch at p — score m (L - 1) + mm + both end
+// bonuses, mm the score of the graph's character against the read's — the strict optimum AND what extend() finds (DESIGN.md 3.4
+// "the substitution class").  With lo / hi the smallest / largest score off the matrix' diagonal:
+//  - gap_opening_penalty + m < lo: an alignment with a gap, every other character matched, scores below one mismatch (the deletion
+//    of one graph character inside a homopolymer matches all L characters: m L + gap_opening);
+//  - 2 hi - lo < m: two mismatches score below one;
+//  - hi - lo < m: a child parked at a fork in front of p, with its own mismatch, stays below the head behind p;
+//  - lo + xdrop >= 0: the x-drop does not cut the head at the mismatch.
+// What depends on the read (the thresholds, strictness against stopping in front of p, the extension cut-off of rel_score_cutoff,
+// max_nodes_per_seq_char and max_ram_per_alignment, which ARE tested while the head runs below the best score) is in lane_exact_sub().
+inline bool lane_exact_sub_config(const mgx_config &c, const DevConfig &d, uint32_t labeled_flags) {
+    if (labeled_flags || !lane_exact_config(c, d, labeled_flags)) return false;
+    const char acgt[4] = { 'A', 'C', 'G', 'T' };
+    const int m = c.score_matrix[(int)'A'][(int)'A'];
+    int lo = m, hi = -128;
+    for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y)
+            if (x != y) { const int v = c.score_matrix[(int)acgt[x]][(int)acgt[y]]; lo = std::min(lo, v); hi = std::max(hi, v); }
+    if (!((int64_t)c.gap_opening_penalty + m < lo)) return false;
+    if (!(2 * hi - lo < m) || !(hi - lo < m)) return false;
+    if (!((int64_t)lo + c.xdrop >= 0)) return false;
+    return true;
+}
+// the level the exit runs at when `level` is asked for: 3 falls back to 2 where only lane_exact_config() holds
+inline uint32_t lane_exact_level(const mgx_config &c, const DevConfig &d, uint32_t labeled_flags, uint32_t level) {
+    if (!level || !lane_exact_config(c, d, labeled_flags)) return 0u;
+    return level >= 3u ? (lane_exact_sub_config(c, d, labeled_flags) ? 3u : 2u) : level;
+}
+
 // whether the automatic default of the exact exit (option exact absent) extends to label-aware batches: decided by measurement —
 // four alternating pairs on BASELINE config 3 put the range with the exit wholly above the range without it
 // (profiles/r09_exact_labels_ab_pairs.txt; README.md, "And the label-aware batches")
 constexpr bool LANE_EXACT_AUTO_LABELED = true;
+// whether the automatic default for unlabeled batches is level 3 (the substitution class) instead of 2: decided by measurement —
+// four alternating pairs against the parent commit put the range at level 3 wholly above the parent's, 17.17 - 17.38 against
+// 15.69 - 15.81 x 10^6 reads/s (profiles/r10_exact_sub_ab_pairs.txt).  Label-aware batches stay at level 2.
+constexpr bool LANE_EXACT_AUTO_SUB = true;
 
 // Whether the lane-per-read kernel may run in front of the group kernel for this configuration (every read it cannot finish
 // goes to the group kernel anyway; this only rules out configurations in which its shortcuts would not be exact or no read
@@ -158,11 +203,12 @@ inline bool lane_enabled(const mgx_config &c, const DevConfig &d, uint32_t k, ui
     if (c.left_end_bonus < 0) return no("negative left end bonus");
     if (!(c.rel_score_cutoff >= 0.0 && c.rel_score_cutoff <= 1.0)) return no("rel_score_cutoff outside [0, 1]");
     LP->self_score = m;
-    // (the host model: MGX_EMU_LANE_EXACT=1 / 2 sets the exact exit's level where the configuration allows it; the product's
+    // (the host model: MGX_EMU_LANE_EXACT=1 / 2 / 3 sets the exact exit's level where the configuration allows it; the product's
     // plan_lane() decides by its own rule and overwrites this)
     const char *ex = std::getenv("MGX_EMU_LANE_EXACT");
-    const uint32_t level = (ex && (*ex == '1' || *ex == '2') && !ex[1]) ? (uint32_t)(*ex - '0') : 0u;
-    LP->exact = (level && lane_exact_config(c, d, labeled_flags)) ? level : 0u;
+    const uint32_t level = (ex && *ex >= '1' && *ex <= '3' && !ex[1]) ? (uint32_t)(*ex - '0') : 0u;
+    LP->exact = lane_exact_level(c, d, labeled_flags, level);
+    LP->sub_list = nullptr;
     return true;
 }
 

@@ -362,15 +362,19 @@ static int plan_lane(mgx_aligner *A, AlignPlan &pl) {
                                  pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u)
                  && (A->opt.lane == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16);       // (a small batch: the spread / 64-lane kernels are quicker)
     // The exact exit (lane_read.hpp lane_exact(), k_lane_exact): option exact = 1 / 2 forces it at that level (1: reads whose first
-    // seed spans the query; 2: also the path class), 0 turns it off; automatic: level 2 for the
+    // seed spans the query; 2: also the path class; 3: also the substitution class), 0 turns it off; automatic: level 3
+    // (LANE_EXACT_AUTO_SUB; label-aware batches: 2) for the
     // batches the lane kernel takes of its own accord — a small batch run with lane=1 keeps every read's fate in lane_read_dp()
     // what the tests of its hand-over reasons pin.  (lane_enabled() filled the flag for the host model: decided here.)
     // Label-aware batches (the reads that keep one label all along, lane_exact_class()): under the same rule, where no dummy
     // node's row holds a label (lane_exact_config()); LANE_EXACT_AUTO_LABELED records that the automatic default includes them.
     const uint32_t lflags = pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u;
     const bool exact_auto = pl.n >= (uint64_t)pl.lane_blocks * 16 && (!pl.labeled || LANE_EXACT_AUTO_LABELED);
-    LP.exact = (pl.lane_ok && A->opt.exact != 0 && lane_exact_config(A->cfg, A->dcfg, lflags)
-                && (A->opt.exact >= 1 || exact_auto)) ? (A->opt.exact >= 1 ? (uint32_t)A->opt.exact : 2u) : 0u;
+    // (level 3, the substitution class: unlabeled batches under lane_exact_sub_config(), else 3 means 2 — lane_exact_level())
+    const uint32_t exact_auto_level = (!pl.labeled && LANE_EXACT_AUTO_SUB) ? 3u : 2u;
+    LP.exact = (pl.lane_ok && A->opt.exact != 0 && (A->opt.exact >= 1 || exact_auto))
+                   ? lane_exact_level(A->cfg, A->dcfg, lflags, A->opt.exact >= 1 ? (uint32_t)A->opt.exact : exact_auto_level) : 0u;
+    LP.sub_list = nullptr;
     pl.key_bits = work_key_bits(pl.n) + (LP.exact ? 1 : 0);
     LP.done_key = LP.exact ? 1u << work_key_bits(pl.n) : 0u;
     if (!pl.lane_ok) return MGX_OK;
@@ -641,7 +645,9 @@ static int choose_multi_pass(mgx_aligner *A, const AlignPlan &pl, bool *multi) {
 // of k_lane_exact and k_lane.
 static int prepare_lane(mgx_aligner *A, AlignPlan &pl) {
     LaneParams &LP = pl.LP;
-    if (int rc = A->lane_bail.ensure(pl.n * 4 + 4)) return rc;
+    // (exact level 3: the candidate list of the substitution class, 16 bytes a read at most, lives in the same buffer — k_lane_exact
+    // writes it, k_lane_exact_sub reads it, and only then, behind the sort, k_lane lists the reads it passes on)
+    if (int rc = A->lane_bail.ensure(std::max<uint64_t>(pl.n * 4 + 4, LP.exact >= 3u ? pl.n * sizeof(LaneSubCand) : 0))) return rc;
     if (int rc = A->lane_params.ensure(sizeof(LaneParams))) return rc;
     if (int rc = A->lane_hist.ensure(64 * 8)) return rc;          // ([32 .. 41]: section timers of -DMGX_LANE_TIMERS builds, [LANE_HIST_EXACT])
     HIP_TRY(hipMemsetAsync(A->lane_hist.p, 0, 64 * 8, A->hstream));
@@ -650,6 +656,7 @@ static int prepare_lane(mgx_aligner *A, AlignPlan &pl) {
     LP.iv[0] = A->iv_fwd.as<uint32_t>(); LP.iv[1] = A->iv_rc.as<uint32_t>();
     LP.scratch = A->lane_scratch.as<uint8_t>();
     LP.bail_list = A->lane_bail.as<uint32_t>();
+    LP.sub_list = A->lane_bail.as<LaneSubCand>();
     LP.bail_count = cursor(A, CUR_LANE_BAIL);
     LP.done_count = cursor(A, CUR_LANE_DONE);
     LP.bail_hist = A->lane_hist.as<unsigned long long>();
@@ -666,14 +673,23 @@ static int exact_by_lanes(mgx_aligner *A, AlignPlan &pl) {
     HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)pl.cus * 4 * 8 * 4, (pl.n + 63) / 64);
     if (int rc = mgx_launch_lane_exact(A->lane_params.p, blocks, pl.labeled ? 1 : 0, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit: %d", rc);
+    // level 3 (unlabeled batches): k_lane_exact listed the candidates of the substitution class; k_lane_exact_sub walks them, a lane
+    // each, taking their number from device memory — sized for the most there can be, its wavefronts leave at once where there are fewer
+    if (LP.exact >= 3u && !pl.labeled) {
+        if (int rc = mgx_launch_lane_exact_sub(A->lane_params.p, blocks, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit (substitutions): %d", rc);
+    }
     unsigned long long done = 0;
-    HIP_TRY(copy_sync(A, &done, cursor(A, CUR_LANE_DONE), 8, hipMemcpyDeviceToHost));      // (synchronises with the kernel)
+    HIP_TRY(copy_sync(A, &done, cursor(A, CUR_LANE_DONE), 8, hipMemcpyDeviceToHost));      // (synchronises with the kernels)
     pl.n_exact = done;
-    unsigned long long path = 0;      // ... of them in the path class (level 2): counted apart, the first-seed-spans class keeps its counter
+    // ... of them in the path class (level 2) and in the substitution class (level 3): counted apart, the first-seed-spans class keeps
+    // its counter (two neighbouring words of the histogram, one copy)
+    static_assert(LANE_HIST_EXACT_SUB == LANE_HIST_EXACT_PATH + 1, "read back together");
+    unsigned long long apart[2] = { 0, 0 };
     if (LP.exact >= 2u && done)
-        HIP_TRY(copy_sync(A, &path, A->lane_hist.as<unsigned long long>() + LANE_HIST_EXACT_PATH, 8, hipMemcpyDeviceToHost));
-    A->lane_exact = done - path;
-    A->lane_exact_path = path;
+        HIP_TRY(copy_sync(A, apart, A->lane_hist.as<unsigned long long>() + LANE_HIST_EXACT_PATH, LP.exact >= 3u ? 16 : 8, hipMemcpyDeviceToHost));
+    A->lane_exact = done - apart[0] - apart[1];
+    A->lane_exact_path = apart[0];
+    A->lane_exact_sub = apart[1];
     return MGX_OK;
 }
 
@@ -859,7 +875,7 @@ static int run_align(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offse
     A->n_passes = 1;
     A->lane_done = 0;
     A->lane_exact = 0;
-    A->lane_exact_path = 0;
+    A->lane_exact_path = A->lane_exact_sub = 0;
     memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
     // (with the exact exit the choice of the multi-pass extension comes before the sort: the exit belongs to the lane kernel's path)
     bool multi = false;
@@ -891,7 +907,7 @@ int run_seeding(mgx_aligner *A, const char *d_seqs, const uint64_t *d_offsets, u
     if (int rc = seed_stage(A, d_seqs, d_offsets, n, Lmax, false, pl)) return rc;
     for (AlignEvent e : { EV_SORTED, EV_LANE_END, EV_ALIGN_END }) HIP_TRY(hipEventRecord(A->ev[e], A->hstream));      // (what collect_stats reads)
     A->n_passes = 0;
-    A->lane_done = A->lane_exact = A->lane_exact_path = 0;
+    A->lane_done = A->lane_exact = A->lane_exact_path = A->lane_exact_sub = 0;
     memset(A->lane_hist_h, 0, sizeof(A->lane_hist_h));
     unsigned long long wanted = 0;
     HIP_TRY(copy_sync(A, &wanted, cursor(A, CUR_SEED), 8, hipMemcpyDeviceToHost));
@@ -916,6 +932,7 @@ int collect_stats(mgx_aligner *A, bool mapped, bool aligned) {
     s.n_lane_reads = A->lane_done;
     s.n_lane_exact_reads = A->lane_exact;
     s.n_lane_exact_path_reads = A->lane_exact_path;
+    s.n_lane_exact_sub_reads = A->lane_exact_sub;
     s.n_lane_lines = ks.lane_lines; s.n_lane_columns = ks.lane_columns;
     for (int x = 0; x < 32; ++x) s.lane_bail_reads[x] = A->lane_hist_h[x];
     if (int on; aligned && A->seedlane_launched && env_int("MGX_SL_TIMERS", &on)) {
@@ -997,7 +1014,7 @@ int mgx_aligner_set_pipeline(mgx_aligner *A, const char *name) {
         else if (key == "no_flat") o.no_flat = v;
         else if (key == "lane") o.lane = v;
         else if (key == "exact") {
-            if (v < -1 || v > 2) return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
+            if (v < -1 || v > 3) return fail(MGX_ERR_INVALID, "unknown option '%s'", name);
             o.exact = v;
         }
         else if (key == "device_share") o.device_share = std::max(1, std::min(v, 64));

@@ -172,8 +172,27 @@ __device__ __forceinline__ void lane_exact_body(const LaneParams &LP) {
         LaneResult R;
         R.words = 0;
         LV<bool> hv;
-        const int cls = read < n_reads ? lane_exact_t<LABELED>(LP, read, R) : LANE_EXACT_NONE;
-        hv.v = cls != LANE_EXACT_NONE;
+        int32_t run_lo = 0, run_hi = 0;
+        const int cls = read < n_reads ? lane_exact_t<LABELED>(LP, read, R, run_lo, run_hi) : LANE_EXACT_NONE;
+        if constexpr (!LABELED) {
+            // level 3: the candidates of the substitution class go on a list for k_lane_exact_sub — one atomic per wavefront — which
+            // walks them side by side; nothing of theirs is written here
+            LV<bool> cv;
+            cv.v = cls == LANE_EXACT_SUB;
+            const uint64_t cm = wave_ballot(cv);
+            if (cm) {
+                LV<uint64_t> pv;
+                pv.v = 0;
+                if (lane == 0) pv.v = atomicAdd(LP.bail_hist + LANE_HIST_SUB_CAND, (unsigned long long)popc64(cm));
+                const uint64_t p0 = wave_bcast(pv, 0) + (uint64_t)popc64(cm & ((1ull << lane) - 1));
+                if (cv.v) {
+                    LaneSubCand c;
+                    c.read = (uint32_t)read; c.strand = (uint32_t)R.strand; c.lo = (uint32_t)run_lo; c.hi = (uint32_t)run_hi;
+                    gst(LP.sub_list + p0, c);
+                }
+            }
+        }
+        hv.v = cls == LANE_EXACT_SPAN || cls == LANE_EXACT_PATH;
         if (!wave_ballot(hv)) continue;
         // output-stream words of the wavefront's reads: one atomic, a prefix sum over the lanes (as k_lane)
         LV<int32_t> wv;
@@ -203,6 +222,68 @@ __device__ __forceinline__ void lane_exact_body(const LaneParams &LP) {
 }
 
 __global__ void __launch_bounds__(64) k_lane_exact(const LaneParams *__restrict__ LPp) { lane_exact_body<false>(*LPp); }
+
+// The substitution class (lane_read.hpp lane_exact_sub(); LaneParams::exact >= 3), behind k_lane_exact and before the work sort:
+// one lane per candidate of LaneParams::sub_list, grid-stride, the count read from device memory (bail_hist[LANE_HIST_SUB_CAND]: no
+// host read-back between the two kernels).  The lanes that walk sit side by side: in k_lane_exact a walking lane would have its
+// 63 wave-mates wait out up to k + 1 dependent graph steps.  The walked nodes stay in LDS until every test has passed; only then
+// is the stream cursor advanced (one atomic per wavefront) and the read written, with the work key that takes it out of k_lane's
+// launch.  A candidate that fails is left as it was: k_lane aligns it.
+__global__ void __launch_bounds__(64) k_lane_exact_sub(const LaneParams *__restrict__ LPp) {
+    const LaneParams &LP = *LPp;
+    __shared__ uint32_t s_walk[LANE_SUB_MAX_WALK][64];
+    const int lane = (int)threadIdx.x;
+    const uint64_t n_cand = (uint64_t)gld(LP.bail_hist + LANE_HIST_SUB_CAND);
+    LaneChip chip;
+    chip.lane = lane; chip.qw = nullptr; chip.qstride = 0; chip.cold = &s_walk[0][lane]; chip.cstride = 64;
+    LineCtr lc = { 0, 0, 0 };
+    uint32_t n_done = 0, n_cap = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_cand; base += (uint64_t)gridDim.x * 64) {
+        const uint64_t at = base + (uint64_t)lane;
+        LaneResult R;
+        R.words = 0;
+        LV<bool> hv;
+        hv.v = false;
+        uint64_t read = 0;
+        if (at < n_cand) {
+            const LaneSubCand c = gld(LP.sub_list + at);
+            read = c.read;
+            hv.v = lane_exact_sub(LP, read, (int)c.strand, (int32_t)c.lo, (int32_t)c.hi, chip.cold, chip.cstride, R, lc);
+        }
+        if (!wave_ballot(hv)) continue;
+        LV<int32_t> wv;
+        wv.v = hv.v ? (int32_t)R.words : 0;
+        const LV<int32_t> pre = wave_prefix_sum_excl(wv);
+        const int32_t total = wave_sum(wv);
+        LV<uint64_t> sv;
+        sv.v = 0;
+        if (lane == 0) sv.v = atomicAdd(LP.P.out_cursor, (unsigned long long)total);
+        const uint64_t so = wave_bcast(sv, 0) + (uint64_t)pre.v;
+        if (hv.v) {
+            lane_emit_t<true, true>(LP, read, nullptr, chip, R, so);
+            gst(LP.P.work_key + read, LP.done_key);
+            ++n_done; n_cap += (uint32_t)(R.rr.status != ST_OK);
+        }
+    }
+    LV<int32_t> v;
+    v.v = (int32_t)n_done; const int32_t nd = wave_sum(v);
+    v.v = (int32_t)n_cap; const int32_t nc = wave_sum(v);
+    v.v = (int32_t)(lc.rank_lines + lc.bit_lines); const int32_t rl = wave_sum(v);
+    v.v = (int32_t)lc.select_lines; const int32_t sl = wave_sum(v);
+    if (lane == 0) {
+        if (nd) {
+            atomicAdd(LP.done_count, (unsigned long long)nd);
+            atomicAdd(LP.bail_hist + LANE_HIST_EXACT, (unsigned long long)nd);
+            atomicAdd(LP.bail_hist + LANE_HIST_EXACT_SUB, (unsigned long long)nd);
+        }
+        if (nc) atomicAdd(&LP.P.stats->capacity_errors, (unsigned long long)nc);
+        if (rl | sl) {
+            atomicAdd(&LP.P.stats->rank_lines, (unsigned long long)rl);
+            atomicAdd(&LP.P.stats->select_lines, (unsigned long long)sl);
+            atomicAdd(&LP.P.stats->lane_lines, (unsigned long long)rl + (unsigned long long)sl);
+        }
+    }
+}
 __global__ void __launch_bounds__(64) k_lane_exact_labeled(const LaneParams *__restrict__ LPp) { lane_exact_body<true>(*LPp); }
 
 // blocks = resident wavefronts (wavefront b owns LaneParams::scratch + b * wave_stride)
@@ -217,6 +298,11 @@ extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stre
 extern "C" int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, int labeled, void *stream) {
     if (labeled) k_lane_exact_labeled<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     else k_lane_exact<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
+    return (int)hipGetLastError();
+}
+// the substitution class, behind mgx_launch_lane_exact on the same stream (LaneParams::exact >= 3, unlabeled batches)
+extern "C" int mgx_launch_lane_exact_sub(const void *d_params, uint32_t blocks, void *stream) {
+    k_lane_exact_sub<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     return (int)hipGetLastError();
 }
 extern "C" int mgx_lane_waves_per_simd(void) { return MGX_LANE_WAVES_PER_SIMD; }

@@ -51,7 +51,7 @@ while time.time() - t0 < 60 * minutes:
             assert got[q] == want[q], ("MISMATCH", seed, q, reads[q], got[q], want[q])
         st = A.stats()
         worlds += 1; reads_total += len(reads); lane_total += st["n_lane_reads"]
-        exact_total += st["n_lane_exact_reads"] + st["n_lane_exact_path_reads"]
+        exact_total += st["n_lane_exact_reads"] + st["n_lane_exact_path_reads"] + st["n_lane_exact_sub_reads"]
         A.close()
         seed += 1
         continue
@@ -83,7 +83,7 @@ while time.time() - t0 < 60 * minutes:
         assert got[q] == want[q], ("MISMATCH", seed, q, reads[q], got[q], want[q])
     st = A.stats()
     worlds += 1; reads_total += len(reads); lane_total += st["n_lane_reads"]
-    exact_total += st["n_lane_exact_reads"] + st["n_lane_exact_path_reads"]
+    exact_total += st["n_lane_exact_reads"] + st["n_lane_exact_path_reads"] + st["n_lane_exact_sub_reads"]
     A.close()
     seed += 1
 print("ok%s: %d worlds (seeds from %d), %d reads, %d finished by the lane kernels%s, no difference"
