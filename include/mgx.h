@@ -259,9 +259,10 @@ typedef struct mgx_stats {
                                    merge, every k-mer of the strand is a node; the same closed form over the strand's mapped nodes.
                                    Both counters count label-aware reads too (k_lane_exact_labeled: one label all along) */
     uint64_t n_lane_exact_sub_reads; /* part of n_lane_reads, none of them in the two counters above: reads finished through the exit's
-                                   substitution class (exact level 3, unlabeled batches; k_lane_exact_sub): the strand's node array has
-                                   one run of zeros behind its first entry, the graph walk across it succeeds, and the result is the
-                                   alignment with one mismatch over the mapped and the walked nodes */
+                                   substitution class (exact level 3; k_lane_exact_sub, label-aware batches k_lane_exact_sub_labeled):
+                                   the strand's node array has one run of zeros behind its first entry, the graph walk across it
+                                   succeeds, and the result is the alignment with one mismatch over the mapped and the walked nodes;
+                                   label-aware: the read keeps one label L along the mapped and the walked nodes, label list [L] */
 } mgx_stats;
 enum { MGX_KERNEL_GRP8 = 1, MGX_KERNEL_GRP8_PRIM = 2, MGX_KERNEL_GRP8_ALT = 4, MGX_KERNEL_EXT64 = 8, MGX_KERNEL_LANE = 16,
        MGX_KERNEL_LAB64 = 32, MGX_KERNEL_GRP8_LAB = 64, /* the label-aware builds of the 64-lane and the 8-lane kernel */
@@ -428,13 +429,14 @@ void mgx_kernel_launch_counts(uint64_t *out5);
  *   exact=0|1|2|3        the lane kernel's exact exit: reads whose result is known when seeding ends are finished in closed form,
  *                        without DP.  1: reads whose first seed spans the query; 2: also reads whose first seed starts at the query's
  *                        first character and whose every k-mer is a node (perfect reads that cross a fork or a merge); 3: also reads
- *                        with one substitution behind their first k characters, where the graph walk across it succeeds (unlabeled
- *                        batches whose scores make that alignment the strict optimum; elsewhere 3 means 2).  Default:
- *                        automatic — level 3 (label-aware batches: 2) for the batches the lane kernel takes of its own accord;
+ *                        with one substitution behind their first k characters, where the graph walk across it succeeds
+ *                        (batches whose scores make that alignment the strict optimum; elsewhere 3 means 2).  Default:
+ *                        automatic — level 3 for the batches the lane kernel takes of its own accord, label-aware ones included;
  *                        1 / 2 / 3: wherever the lane kernel runs and the configuration allows it.  Label-aware batches (wherever the lane kernel takes them:
- *                        no dummy node's row holds a label) are included, at either level and in the automatic default: there
+ *                        no dummy node's row holds a label) are included, at every level and in the automatic default: there
  *                        the exit takes the reads that keep one label all along — the label filter leaves the seeds one label L
- *                        and every node of the path has the row { L } — and the label list of the alignment is [L]; with one
+ *                        and every node of the path (at level 3: the nodes walked across the substitution too) has the row { L }
+ *                        — and the label list of the alignment is [L]; with one
  *                        seed per k-mer the first class is the reads of k characters.  Results never depend on the option
  *   device_share=n       n handles are at work on this device at the same time (worker threads): this handle sizes its per-slot
  *                        arenas for 1 / n of the machine (default 1: all of it)

@@ -134,6 +134,8 @@ class Stats(C.Structure):
                 ("lane_bail_reads", C.c_uint64 * 32), ("n_capacity_retried", C.c_uint64),
                 ("n_seed_lane_reads", C.c_uint64), ("seed_lane_ms", C.c_double), ("seed_lane_left_reads", C.c_uint64 * 16),
                 ("n_lane_exact_reads", C.c_uint64), ("n_lane_exact_path_reads", C.c_uint64),
+                # (the exact exit's classes, each part of n_lane_reads and counted once: a spanning first seed, the path class,
+                # the substitution class; label-aware batches count in all three — option exact, include/mgx.h)
                 ("n_lane_exact_sub_reads", C.c_uint64)]
 
 

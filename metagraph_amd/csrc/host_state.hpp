@@ -310,9 +310,10 @@ struct mgx_aligner {
                                   // that finds no room goes on without a seed limit in the same launch
         int no_compact = 0, no_alias = 0, no_bt_runs = 0, no_flat = 0;
         int lane = -1;            // the lane-per-read kernel in front of the extension kernel: -1 auto, 0 off, 1 forced
-        int exact = -1;           // the lane kernel's exact exit (k_lane_exact, no DP): -1 auto (level 2 for the batches the lane kernel
-                                  // takes of its own accord), 0 off, 1 / 2 that level wherever the lane kernel runs (1: reads whose
-                                  // first seed spans the query; 2: also reads whose every k-mer is a node, the path class);
+        int exact = -1;           // the lane kernel's exact exit (k_lane_exact, no DP): -1 auto (level 3 for the batches the lane kernel
+                                  // takes of its own accord), 0 off, 1 / 2 / 3 that level wherever the lane kernel runs (1: reads whose
+                                  // first seed spans the query; 2: also reads whose every k-mer is a node, the path class; 3: also
+                                  // reads with one substitution, the substitution class);
                                   // label-aware batches included (the reads that keep one label all along)
         int seed_lane = -1;       // the lane-per-read seeder in front of the seeding kernel (seed_lane.hpp): -1 auto, 0 off, 1 forced
         int seed_wps = 8;         // wavefronts per SIMD of the short-read seeding kernel: 8 (64 VGPRs, spills) or 4 (102 VGPRs, tables in LDS)

@@ -77,7 +77,7 @@ int mgx_seed_load(void);
 // mgx_lane.hip: the lane-per-read kernel.  d_params: LaneParams in DEVICE memory; blocks = resident wavefronts
 int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream);
 int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, int labeled, void *stream);    // k_lane_exact / k_lane_exact_labeled, before the work sort when LaneParams::exact
-int mgx_launch_lane_exact_sub(const void *d_params, uint32_t blocks, void *stream);             // k_lane_exact_sub, behind k_lane_exact when LaneParams::exact >= 3
+int mgx_launch_lane_exact_sub(const void *d_params, uint32_t blocks, int labeled, void *stream); // k_lane_exact_sub / k_lane_exact_sub_labeled, behind those when LaneParams::exact >= 3
 int mgx_lane_waves_per_simd(void);
 
 // mgx_seedlane.hip: the lane-per-read seeder.  d_params: SeedLaneParams in DEVICE memory; long_reads: the build for reads of

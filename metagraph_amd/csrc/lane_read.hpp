@@ -338,6 +338,8 @@ struct LaneResult {
     int32_t score, offset, clip, end_clip, n_runs, j_hi, n_nodes, n_seq, trim, strand;      // j_hi: last column of the path; trim: nodes trim_offset dropped
     uint32_t words;                      // words of the output stream the alignment takes
     uint32_t label;                      // label-aware: the alignment's one label
+    uint32_t sub_code;                   // the substitution class of a label-aware batch (lane_exact_sub<true>()): the graph's character
+                                         // code at the mismatch, which an unlabeled batch keeps in `label`
 };
 
 // One read.  `item`: its position in the launch (tags the node table).  scratch: the wavefront's LaneParams::scratch from this
@@ -1412,10 +1414,12 @@ MGX_DEV int lane_read_dp(const LaneParams &LP, uint64_t read, const uint32_t ite
 // the later seeds, whose last nodes lie on this path with the full prefix score, are found dead by check_seed.  Same score, same
 // CIGAR; the nodes are the strand's mapped nodes, which is where LANE_EMIT_EXACT takes them from anyway.
 //
-// The substitution class (LaneParams::exact >= 3, unlabeled batches): the header tests hold, and the strand's node array has exactly
+// The substitution class (LaneParams::exact >= 3): the header tests hold, and the strand's node array has exactly
 // one run of zeros [lo, hi], lo >= 1, of k entries (or reaching the array's end) — the k-mers that cover one query position
 // p = lo + k - 1.  lane_exact_class() returns LANE_EXACT_SUB for such a CANDIDATE without filling anything; lane_exact_sub() walks
-// the graph across the run and decides (the conditions and why they carry the closed form: there and DESIGN.md 3.4).
+// the graph across the run and decides (the conditions and why they carry the closed form: there and DESIGN.md 3.4).  Label-aware
+// batches: the header tests are those of the label-aware path class (the filter's label L, counts and strand), and every node of
+// the path — mapped and walked — has the row { L }.
 enum { LANE_EXACT_NONE = 0, LANE_EXACT_SPAN = 1, LANE_EXACT_PATH = 2, LANE_EXACT_SUB = 3 };
 
 // whether none of the n node indices at p is 0 (a k-mer that is not in the graph), with the widest loads p's alignment allows:
@@ -1524,23 +1528,39 @@ MGX_DEV bool lane_exact_label_filter(const AlignParams &P, const uint64_t read, 
 // pass (a k-mer that is not in the graph fails with the rest).  Four nodes to a 16-byte load as lane_all_nodes(), then their four
 // rows requested before the first is looked at: the gathers are independent, a round trip each, and one at a time a lane would
 // wait ~120 of them out in a row.  Leaves at the first group that fails.
-MGX_DEV bool lane_all_rows(const AlignParams &P, const uint32_t *p, const int32_t n, const uint32_t label) {
+// [slo, shi]: entries left out of the test (a candidate of the substitution class: its run of zeros, whose nodes the walk has yet
+// to find); none by default.  A group of four that the range cuts keeps its four gathers in flight: an entry left out asks for
+// the row of a neighbour that is tested anyway.
+MGX_DEV bool lane_all_rows(const AlignParams &P, const uint32_t *p, const int32_t n, const uint32_t label, const int32_t slo = 0,
+                           const int32_t shi = -1) {
     const uint64_t want = ((uint64_t)label << 16) | 1u, gn = P.g.n, rows = P.anno_rows;
     const uint64_t *head = P.anno_head;
     auto row_ok = [&](const uint32_t node) -> bool { return node && node <= gn && (uint64_t)node - 1 < rows; };
+    auto out = [&](const int32_t at) -> bool { return at >= slo && at <= shi; };
     int32_t x = 0;
     for (; x < n && ((uintptr_t)(p + x) & 15u); ++x) {
+        if (out(x)) continue;
         const uint32_t v = gld(p + x);
         if (!row_ok(v) || gld(head + ((uint64_t)v - 1)) != want) return false;
     }
     for (; x + 4 <= n; x += 4) {
-        const LaneNodeQuad q = gld((const LaneNodeQuad *)(p + x));
+        if (x >= slo && x + 3 <= shi) continue;
+        LaneNodeQuad q = gld((const LaneNodeQuad *)(p + x));
+        if (x + 3 >= slo && x <= shi) {
+            // (the range cuts this group: at least one of its entries is outside it)
+            uint32_t any = 0;
+            for (int t = 0; t < 4; ++t)
+                if (!out(x + t)) any = q.v[t];
+            for (int t = 0; t < 4; ++t)
+                if (out(x + t)) q.v[t] = any;
+        }
         if (!row_ok(q.v[0]) || !row_ok(q.v[1]) || !row_ok(q.v[2]) || !row_ok(q.v[3])) return false;
         const uint64_t h0 = gld(head + ((uint64_t)q.v[0] - 1)), h1 = gld(head + ((uint64_t)q.v[1] - 1));
         const uint64_t h2 = gld(head + ((uint64_t)q.v[2] - 1)), h3 = gld(head + ((uint64_t)q.v[3] - 1));
         if (((h0 ^ want) | (h1 ^ want) | (h2 ^ want) | (h3 ^ want)) != 0) return false;
     }
     for (; x < n; ++x) {
+        if (out(x)) continue;
         const uint32_t v = gld(p + x);
         if (!row_ok(v) || gld(head + ((uint64_t)v - 1)) != want) return false;
     }
@@ -1553,7 +1573,8 @@ MGX_DEV bool lane_all_rows(const AlignParams &P, const uint32_t *p, const int32_
 // that passed them all and whose first seed ends short of the query, and the rows along the path (label-aware) last of all.
 // LABELED: whether the batch may be label-aware (k_lane_exact, the kernel of the unlabeled batches, is compiled without that half:
 // its code is what it was); a label-aware batch under LABELED = false is refused.
-// run_lo / run_hi (level 3, unlabeled): for LANE_EXACT_SUB the run of zeros of a candidate of the substitution class.
+// run_lo / run_hi (level 3): for LANE_EXACT_SUB the run of zeros of a candidate of the substitution class.  Label-aware, the rows
+// of the mapped nodes on both sides of the run have been tested then, the walked nodes' rows are lane_exact_sub()'s to test.
 template <bool LABELED>
 MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t *L_out, int *strand, uint32_t hdr4[4], uint32_t *label_out,
                              int32_t &run_lo, int32_t &run_hi) {
@@ -1606,7 +1627,7 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
     const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
     const int32_t nk = L - k + 1;
     int cls = len == L ? LANE_EXACT_SPAN : LANE_EXACT_PATH;
-    if (!LABELED && len != L && LP.exact >= 3u) {
+    if ((!LABELED || labeled) && len != L && LP.exact >= 3u) {
         // level 3: one scan tells the path class (no zero) from a candidate of the substitution class (one run of zeros behind
         // index 0: k entries, or up to k that reach the array's end — a longer run there covers a second mismatch) from the rest
         int32_t lo = -1, hi = -1;
@@ -1618,7 +1639,7 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
             cls = LANE_EXACT_SUB;
         }
     }
-    if ((LABELED || LP.exact < 3u) && len != L) {
+    if ((LABELED ? cls != LANE_EXACT_SUB : LP.exact < 3u) && len != L) {
         // the path class.  The k-mer behind the seed's last one first: where the seed ended at a character the graph does not
         // have — most reads that come this far and are not in the class — that one word settles it
         const int32_t next = len - k + 1;
@@ -1626,8 +1647,10 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
         if (!labeled && !lane_all_nodes(rn, nk)) return LANE_EXACT_NONE;
     }
     // label-aware: every node of the path has the row { label } — in the span class too: the filter saw each seed's first node
-    // only — and, in the path class, is a node at all: one pass over the node array
-    if (labeled && !lane_all_rows(P, rn, nk, label)) return LANE_EXACT_NONE;
+    // only — and, in the path class, is a node at all: one pass over the node array.  A candidate of the substitution class goes
+    // through the same pass, its run of zeros left out: its lanes share the instruction stream of their wave-mates' path-class reads
+    if (labeled && !lane_all_rows(P, rn, nk, label, cls == LANE_EXACT_SUB ? run_lo : 0, cls == LANE_EXACT_SUB ? run_hi : -1))
+        return LANE_EXACT_NONE;
     *L_out = L; *strand = s; *label_out = label;
     hdr4[0] = nm0; hdr4[1] = nm1; hdr4[2] = (uint32_t)ns0; hdr4[3] = (uint32_t)ns1;
     return cls;
@@ -1636,7 +1659,8 @@ MGX_DEV int lane_exact_class(const LaneParams &LP, const uint64_t read, int32_t 
 // Returns the class if R is filled (as lane_read_dp() fills it for LR_DONE; no extension ran: n_extensions = n_columns = 0),
 // else LANE_EXACT_NONE.  The closed form is the same for both classes; label-aware it carries the read's one label behind it.
 // LANE_EXACT_SUB: a candidate of the substitution class — nothing filled but R.strand and the run of zeros: the caller
-// lists it for k_lane_exact_sub (mgx_lane.hip) or, in the host model, calls lane_exact_sub() (below).
+// lists it for k_lane_exact_sub (mgx_lane.hip) or, in the host model, calls lane_exact_sub() (below).  Label-aware also R.label
+// and the four header words of R.rr as the label filter left them: lane_exact_sub<true>() takes them from there.
 template <bool LABELED>
 MGX_DEV int lane_exact_t(const LaneParams &LP, const uint64_t read, LaneResult &R, int32_t &run_lo, int32_t &run_hi) {
     int32_t L = 0;
@@ -1644,7 +1668,14 @@ MGX_DEV int lane_exact_t(const LaneParams &LP, const uint64_t read, LaneResult &
     uint32_t h[4], label = 0;
     const int cls = lane_exact_class<LABELED>(LP, read, &L, &s, h, &label, run_lo, run_hi);
     if (cls == LANE_EXACT_NONE) return cls;
-    if (cls == LANE_EXACT_SUB) { R.strand = s; return cls; }
+    if (cls == LANE_EXACT_SUB) {
+        R.strand = s;
+        if constexpr (LABELED) {
+            R.label = label;
+            R.rr.num_matches_fwd = h[0]; R.rr.num_matches_rc = h[1]; R.rr.n_seeds_fwd = h[2]; R.rr.n_seeds_rc = h[3];
+        }
+        return cls;
+    }
     const int32_t k = (int32_t)LP.P.g.k;
     ReadResult &rr = R.rr;
     rr.status = ST_OK; rr.n_alignments = 0; rr.score = 0; rr.offset = 0; rr.n_nodes = rr.n_cigar = rr.seq_len = 0;
@@ -1724,6 +1755,14 @@ MGX_DEV int lane_sub_children(const DevGraph &g, const uint32_t v, uint32_t *fir
 //     takes its nodes from the array, outside the run; one with an offset carries its node: compared) and the path's prefix score
 //     there, m (lpos + 1) + left_end_bonus (+ mm - m from p on), is not below the seed's own m length (+ left_end_bonus at clipping 0).
 //  6. The class score passes min_path_score and min_cell_score.
+// LABELED (a label-aware batch; k_lane_exact_sub_labeled and the host model): R comes in as lane_exact_t<true>() left it for a
+// candidate — R.label the filter's label L, the four header words of R.rr the filtered counts — and lane_exact_class<true>() has
+// tested the rows of the mapped nodes.  Added here:
+//  7. every walked node has the row { L } (head word (L << 16) | 1), the gathers requested four at a time as lane_all_rows() does.
+// 1 and 2a stay tests on the plain graph (LabeledExtender::call_outgoing only removes children), 5 runs over the strand's seeds,
+// all of which the filter kept or it would have emptied the strand.  The graph's character goes to R.sub_code, R.label stays L, and
+// the stream takes two words more (label count 1, L).  Why 3 - 5 survive LabeledExtender: DESIGN.md 3.4.
+template <bool LABELED = false>
 MGX_DEV bool lane_exact_sub(const LaneParams &LP, const uint64_t read, const int s, const int32_t lo, const int32_t hi,
                             uint32_t *walk, const int32_t wstride, LaneResult &R, LineCtr &lc) {
     const AlignParams &P = LP.P;
@@ -1733,6 +1772,7 @@ MGX_DEV bool lane_exact_sub(const LaneParams &LP, const uint64_t read, const int
     const int32_t L = (int32_t)(gld(P.offsets + read + 1) - off);
     const int32_t nk = L - k + 1, p = lo + k - 1;
     if (lo < 1 || hi < lo || hi >= nk || hi - lo + 1 > k || hi - lo + 1 > LANE_SUB_MAX_WALK) return false;
+    const uint32_t label = LABELED ? R.label : 0u;
     const uint32_t *rn = (s ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
     const uint64_t wb = packed_word_begin(off, read);
     const uint64_t *pw = LP.pk[s] + wb;
@@ -1766,6 +1806,24 @@ MGX_DEV bool lane_exact_sub(const LaneParams &LP, const uint64_t read, const int
         const uint32_t nx = lane_sub_step(P.g, cur, qcode(p + k), lc);
         if (!nx || nx != gld(rn + hi + 1)) return false;
     }
+    if constexpr (LABELED) {
+        // 7. the walked nodes' rows (each is a node of the graph: lane_sub_step() returned it)
+        const uint64_t want = ((uint64_t)label << 16) | 1u, rows = P.anno_rows;
+        const uint64_t *head = P.anno_head;
+        const int32_t nw = hi - lo + 1;
+        int32_t x = 0;
+        for (; x + 4 <= nw; x += 4) {
+            const uint64_t i0 = (uint64_t)walk[x * wstride] - 1, i1 = (uint64_t)walk[(x + 1) * wstride] - 1;
+            const uint64_t i2 = (uint64_t)walk[(x + 2) * wstride] - 1, i3 = (uint64_t)walk[(x + 3) * wstride] - 1;
+            if (i0 >= rows || i1 >= rows || i2 >= rows || i3 >= rows) return false;
+            const uint64_t h0 = gld(head + i0), h1 = gld(head + i1), h2 = gld(head + i2), h3 = gld(head + i3);
+            if (((h0 ^ want) | (h1 ^ want) | (h2 ^ want) | (h3 ^ want)) != 0) return false;
+        }
+        for (; x < nw; ++x) {
+            const uint64_t i0 = (uint64_t)walk[x * wstride] - 1;
+            if (i0 >= rows || gld(head + i0) != want) return false;
+        }
+    }
     // 2a. a run shorter than k (it reaches the array's end): no fork in front of the mismatch inside the last k characters
     for (int32_t x = imax(L - 2 * k, 0); x <= lo - 2; ++x) {
         uint32_t f = 0, fc = 0;
@@ -1794,13 +1852,16 @@ MGX_DEV bool lane_exact_sub(const LaneParams &LP, const uint64_t read, const int
     ReadResult &rr = R.rr;
     rr.status = ST_OK; rr.n_alignments = 0; rr.score = 0; rr.offset = 0; rr.n_nodes = rr.n_cigar = rr.seq_len = 0;
     rr.orientation = 0; rr.stream_off = 0;
-    rr.num_matches_fwd = gld(&hp->num_matching[0]); rr.num_matches_rc = gld(&hp->num_matching[1]);
-    rr.n_seeds_fwd = (uint32_t)ns0; rr.n_seeds_rc = (uint32_t)ns1;
+    if constexpr (!LABELED) {            // (label-aware: the four words are in R.rr already, as the filter left them)
+        rr.num_matches_fwd = gld(&hp->num_matching[0]); rr.num_matches_rc = gld(&hp->num_matching[1]);
+        rr.n_seeds_fwd = (uint32_t)ns0; rr.n_seeds_rc = (uint32_t)ns1;
+    }
     rr.n_extensions = 0; rr.n_columns = 0;
-    R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0; R.label = g;
+    R.have_aln = 1; R.mode = LANE_EMIT_EXACT; R.strand = s; R.trim = 0;
+    if constexpr (LABELED) { R.label = label; R.sub_code = g; } else R.label = g;
     R.score = score;
     R.offset = 0; R.clip = 0; R.end_clip = 0; R.n_runs = p == L - 1 ? 2 : 3; R.j_hi = p; R.n_nodes = nk; R.n_seq = L;
-    R.words = (uint32_t)R.n_nodes + (uint32_t)R.n_runs + ((uint32_t)L + 3) / 4;
+    R.words = (uint32_t)R.n_nodes + (uint32_t)R.n_runs + ((uint32_t)L + 3) / 4 + (LABELED ? 2u : 0u);
     return true;
 }
 static_assert(LANE_COLD_WORDS >= LANE_SUB_MAX_WALK, "the host model keeps a walk in the lane's cold words");
@@ -1813,7 +1874,8 @@ MGX_DEV int lane_exact_walked(const LaneParams &LP, const uint64_t read, LaneRes
     if (cls != LANE_EXACT_SUB) return cls;
     if (!scratch || !chip.cold) return LANE_EXACT_NONE;
     LineCtr lc = { 0, 0, 0 };
-    const bool ok = lane_exact_sub(LP, read, R.strand, run_lo, run_hi, chip.cold, chip.cstride, R, lc);
+    const bool ok = LP.P.labeled ? lane_exact_sub<true>(LP, read, R.strand, run_lo, run_hi, chip.cold, chip.cstride, R, lc)
+                                 : lane_exact_sub<false>(LP, read, R.strand, run_lo, run_hi, chip.cold, chip.cstride, R, lc);
     uint32_t *rec = lane_record(LP, scratch, chip.lane);
     gst(rec + 27, gld(rec + 27) + lc.rank_lines + lc.bit_lines); gst(rec + 28, gld(rec + 28) + lc.select_lines);
     return ok ? LANE_EXACT_SUB : LANE_EXACT_NONE;
@@ -1838,7 +1900,9 @@ MGX_DEV int lane_read(const LaneParams &LP, uint64_t read, const uint32_t item, 
 // WITH_EXACT: R may be what lane_exact() left (the kernel writes those reads apart, and keeps the closed form's code out of the
 // path behind the DP: k_lane has no register to spare, mgx_lane.hip)
 // WITH_SUB: ... or what lane_exact_sub() left (k_lane_exact_sub and the host model only: the other kernels keep their code)
-template <bool WITH_EXACT, bool WITH_SUB = false>
+// SUB_LABELED: ... in a label-aware batch, lane_exact_sub<true>(): R.label is the label and the graph's character at the mismatch
+// is R.sub_code (k_lane_exact_sub_labeled and the host model only)
+template <bool WITH_EXACT, bool WITH_SUB = false, bool SUB_LABELED = false>
 MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
                          const uint64_t so) {
     const AlignParams &P = LP.P;
@@ -1872,7 +1936,7 @@ MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_
                 const uint32_t *rn = (R.strand ? P.nodes_rc : P.nodes_fwd) + gld(P.node_begin + read);
                 const uint64_t *pw = LP.pk[R.strand] + packed_word_begin(off, read);
                 // (the substitution class, R.n_runs > 1: "p= 1X (L-1-p)=" with p = R.j_hi, the walked nodes from chip.cold in place of
-                // the run of zeros that begins at p - k + 1, the graph's character R.label at p: lane_exact_sub())
+                // the run of zeros that begins at p - k + 1, the graph's character R.label — SUB_LABELED: R.sub_code — at p: lane_exact_sub())
                 const bool sub = WITH_SUB && R.n_runs > 1;
                 const int32_t sp = sub ? R.j_hi : -1, lo = sub ? sp - k_minus_1 : R.n_nodes;
                 for (int32_t x = 0; x < R.n_nodes; ++x) gst(dst + x, (x >= lo && x <= sp) ? chip.cold[(x - lo) * chip.cstride] : gld(rn + x));
@@ -1889,7 +1953,7 @@ MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_
                     if (!(x & 31)) qw = gld(pw + (x >> 5));
                     uint32_t v = 0;
                     for (int t = 0; t < 4; ++t)
-                        if (x + t < R.n_seq) v |= (uint32_t)decode_code(x + t == sp ? R.label : ((uint32_t)(qw >> (2 * ((x + t) & 31))) & 3u) + 1u) << (8 * t);
+                        if (x + t < R.n_seq) v |= (uint32_t)decode_code(x + t == sp ? (SUB_LABELED ? R.sub_code : R.label) : ((uint32_t)(qw >> (2 * ((x + t) & 31))) & 3u) + 1u) << (8 * t);
                     gst(dw + (x >> 2), v);
                 }
             } else if (R.mode == LANE_EMIT_ARRAYS) {
@@ -1952,7 +2016,8 @@ MGX_DEV void lane_emit_t(const LaneParams &LP, const uint64_t read, const uint8_
 
 MGX_DEV void lane_emit(const LaneParams &LP, const uint64_t read, const uint8_t *scratch, const LaneChip &chip, LaneResult &R,
                        const uint64_t so) {
-    lane_emit_t<true, true>(LP, read, scratch, chip, R, so);
+    if (LP.P.labeled) lane_emit_t<true, true, true>(LP, read, scratch, chip, R, so);
+    else lane_emit_t<true, true>(LP, read, scratch, chip, R, so);
 }
 
 } // namespace mgx

@@ -65,16 +65,23 @@ struct LaneParams {
     uint32_t exact;                      // the level of the exact exit (lane_read.hpp; only where lane_exact_config() holds).  1: a read whose
                                          // first seed spans the query is finished without DP; 2: also a read whose first seed starts at
                                          // the query's first character and whose every k-mer is a node (the path class); 3: also a read
-                                         // with one substitution behind its first k characters (the substitution class: unlabeled batches
-                                         // under lane_exact_sub_config() only, label-aware ones stay at 2).  0 by default: every read
-                                         // runs its columns
+                                         // with one substitution behind its first k characters (the substitution class, under
+                                         // lane_exact_sub_config() only; label-aware: the read keeps one label along the walked nodes
+                                         // too).  0 by default: every read runs its columns
     uint32_t done_key;                   // exact, on the device: the work key k_lane_exact gives the reads it finished — above every
                                          // key of the seeding phase, so that the work sort puts them behind the items k_lane is launched on
     struct LaneSubCand *sub_list;        // exact >= 3: the reads that passed the header tests and have one run of zeros in their node
-                                         // array, listed by k_lane_exact for k_lane_exact_sub (bail_hist[LANE_HIST_SUB_CAND] of them)
+                                         // array, listed by k_lane_exact for k_lane_exact_sub (bail_hist[LANE_HIST_SUB_CAND] of them);
+                                         // label-aware batches: LaneSubCandLabeled records at the same address, listed by
+                                         // k_lane_exact_labeled for k_lane_exact_sub_labeled
 };
 // a candidate of the substitution class: the read, the strand aligned, the run of zeros [lo, hi] in that strand's node array
 struct alignas(16) LaneSubCand { uint32_t read, strand, lo, hi; };
+// ... of a label-aware batch (k_lane_exact_labeled lists, k_lane_exact_sub_labeled reads; the same buffer, a record type of its own):
+// also what the one-label seed filter found, which gathered the seeds' rows for it and is not run a second time — the read's
+// label, and num_matching and the seed counts of both strands as the filter left them (the result record's)
+struct alignas(16) LaneSubCandLabeled { uint32_t read, strand, lo, hi, label, nm[2], ns[2], pad[3]; };
+static_assert(sizeof(LaneSubCandLabeled) == 48, "three 16-byte loads");
 constexpr int LANE_HIST_EXACT = 48;        // (bail_hist has 64 words; [32 .. 41] are the section timers of -DMGX_LANE_TIMERS builds)
 constexpr int LANE_HIST_EXACT_PATH = 49;
 constexpr int LANE_HIST_EXACT_SUB = 50;
@@ -133,9 +140,11 @@ inline bool lane_exact_config(const mgx_config &c, const DevConfig &d, uint32_t 
 }
 
 // Whether level 3 of the exact exit (the substitution class, lane_read.hpp lane_exact_sub()) may be on, given lane_exact_config():
-// unlabeled batches only, and the conditions that make the alignment with one mismatch at p — score m (L - 1) + mm + both end
+// the conditions that make the alignment with one mismatch at p — score m (L - 1) + mm + both end
 // bonuses, mm the score of the graph's character against the read's — the strict optimum AND what extend() finds (DESIGN.md 3.4
-// "the substitution class").  With lo / hi the smallest / largest score off the matrix' diagonal:
+// "the substitution class").  Label-aware batches under lane_exact_config()'s label condition: LabeledExtender only takes
+// alternatives away from the plain extender where every node of the path has the row { L } (DESIGN.md 3.4 "the substitution
+// class, label-aware").  With lo / hi the smallest / largest score off the matrix' diagonal:
 //  - gap_opening_penalty + m < lo: an alignment with a gap, every other character matched, scores below one mismatch (the deletion
 //    of one graph character inside a homopolymer matches all L characters: m L + gap_opening);
 //  - 2 hi - lo < m: two mismatches score below one;
@@ -144,7 +153,7 @@ inline bool lane_exact_config(const mgx_config &c, const DevConfig &d, uint32_t 
 // What depends on the read (the thresholds, strictness against stopping in front of p, the extension cut-off of rel_score_cutoff,
 // max_nodes_per_seq_char and max_ram_per_alignment, which ARE tested while the head runs below the best score) is in lane_exact_sub().
 inline bool lane_exact_sub_config(const mgx_config &c, const DevConfig &d, uint32_t labeled_flags) {
-    if (labeled_flags || !lane_exact_config(c, d, labeled_flags)) return false;
+    if (!lane_exact_config(c, d, labeled_flags)) return false;
     const char acgt[4] = { 'A', 'C', 'G', 'T' };
     const int m = c.score_matrix[(int)'A'][(int)'A'];
     int lo = m, hi = -128;
@@ -168,8 +177,11 @@ inline uint32_t lane_exact_level(const mgx_config &c, const DevConfig &d, uint32
 constexpr bool LANE_EXACT_AUTO_LABELED = true;
 // whether the automatic default for unlabeled batches is level 3 (the substitution class) instead of 2: decided by measurement —
 // four alternating pairs against the parent commit put the range at level 3 wholly above the parent's, 17.17 - 17.38 against
-// 15.69 - 15.81 x 10^6 reads/s (profiles/r10_exact_sub_ab_pairs.txt).  Label-aware batches stay at level 2.
+// 15.69 - 15.81 x 10^6 reads/s (profiles/r10_exact_sub_ab_pairs.txt).
 constexpr bool LANE_EXACT_AUTO_SUB = true;
+// ... and whether the automatic default for label-aware batches is level 3 as well (k_lane_exact_sub_labeled) instead of 2: by the
+// same rule, on BASELINE config 3 against the parent commit (profiles/r11_exact_sub_labels_ab_pairs.txt)
+constexpr bool LANE_EXACT_AUTO_SUB_LABELED = true;
 
 // Whether the lane-per-read kernel may run in front of the group kernel for this configuration (every read it cannot finish
 // goes to the group kernel anyway; this only rules out configurations in which its shortcuts would not be exact or no read

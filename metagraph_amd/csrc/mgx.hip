@@ -363,15 +363,15 @@ static int plan_lane(mgx_aligner *A, AlignPlan &pl) {
                  && (A->opt.lane == 1 || pl.n >= (uint64_t)pl.lane_blocks * 16);       // (a small batch: the spread / 64-lane kernels are quicker)
     // The exact exit (lane_read.hpp lane_exact(), k_lane_exact): option exact = 1 / 2 forces it at that level (1: reads whose first
     // seed spans the query; 2: also the path class; 3: also the substitution class), 0 turns it off; automatic: level 3
-    // (LANE_EXACT_AUTO_SUB; label-aware batches: 2) for the
+    // (LANE_EXACT_AUTO_SUB; label-aware batches: LANE_EXACT_AUTO_SUB_LABELED, else 2) for the
     // batches the lane kernel takes of its own accord — a small batch run with lane=1 keeps every read's fate in lane_read_dp()
     // what the tests of its hand-over reasons pin.  (lane_enabled() filled the flag for the host model: decided here.)
     // Label-aware batches (the reads that keep one label all along, lane_exact_class()): under the same rule, where no dummy
     // node's row holds a label (lane_exact_config()); LANE_EXACT_AUTO_LABELED records that the automatic default includes them.
     const uint32_t lflags = pl.labeled ? (1u | (A->anno_dummy_clean ? 2u : 0u)) : 0u;
     const bool exact_auto = pl.n >= (uint64_t)pl.lane_blocks * 16 && (!pl.labeled || LANE_EXACT_AUTO_LABELED);
-    // (level 3, the substitution class: unlabeled batches under lane_exact_sub_config(), else 3 means 2 — lane_exact_level())
-    const uint32_t exact_auto_level = (!pl.labeled && LANE_EXACT_AUTO_SUB) ? 3u : 2u;
+    // (level 3, the substitution class: under lane_exact_sub_config(), else 3 means 2 — lane_exact_level())
+    const uint32_t exact_auto_level = (pl.labeled ? LANE_EXACT_AUTO_SUB_LABELED : LANE_EXACT_AUTO_SUB) ? 3u : 2u;
     LP.exact = (pl.lane_ok && A->opt.exact != 0 && (A->opt.exact >= 1 || exact_auto))
                    ? lane_exact_level(A->cfg, A->dcfg, lflags, A->opt.exact >= 1 ? (uint32_t)A->opt.exact : exact_auto_level) : 0u;
     LP.sub_list = nullptr;
@@ -645,9 +645,11 @@ static int choose_multi_pass(mgx_aligner *A, const AlignPlan &pl, bool *multi) {
 // of k_lane_exact and k_lane.
 static int prepare_lane(mgx_aligner *A, AlignPlan &pl) {
     LaneParams &LP = pl.LP;
-    // (exact level 3: the candidate list of the substitution class, 16 bytes a read at most, lives in the same buffer — k_lane_exact
-    // writes it, k_lane_exact_sub reads it, and only then, behind the sort, k_lane lists the reads it passes on)
-    if (int rc = A->lane_bail.ensure(std::max<uint64_t>(pl.n * 4 + 4, LP.exact >= 3u ? pl.n * sizeof(LaneSubCand) : 0))) return rc;
+    // (exact level 3: the candidate list of the substitution class, one record a read at most — LaneSubCand, label-aware
+    // LaneSubCandLabeled — lives in the same buffer: k_lane_exact writes it, k_lane_exact_sub reads it, and only then, behind the sort,
+    // k_lane lists the reads it passes on)
+    const uint64_t cand_bytes = pl.labeled ? sizeof(LaneSubCandLabeled) : sizeof(LaneSubCand);
+    if (int rc = A->lane_bail.ensure(std::max<uint64_t>(pl.n * 4 + 4, LP.exact >= 3u ? pl.n * cand_bytes : 0))) return rc;
     if (int rc = A->lane_params.ensure(sizeof(LaneParams))) return rc;
     if (int rc = A->lane_hist.ensure(64 * 8)) return rc;          // ([32 .. 41]: section timers of -DMGX_LANE_TIMERS builds, [LANE_HIST_EXACT])
     HIP_TRY(hipMemsetAsync(A->lane_hist.p, 0, 64 * 8, A->hstream));
@@ -673,10 +675,11 @@ static int exact_by_lanes(mgx_aligner *A, AlignPlan &pl) {
     HIP_TRY(copy_sync(A, A->lane_params.p, &LP, sizeof(LP), hipMemcpyHostToDevice));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)pl.cus * 4 * 8 * 4, (pl.n + 63) / 64);
     if (int rc = mgx_launch_lane_exact(A->lane_params.p, blocks, pl.labeled ? 1 : 0, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit: %d", rc);
-    // level 3 (unlabeled batches): k_lane_exact listed the candidates of the substitution class; k_lane_exact_sub walks them, a lane
-    // each, taking their number from device memory — sized for the most there can be, its wavefronts leave at once where there are fewer
-    if (LP.exact >= 3u && !pl.labeled) {
-        if (int rc = mgx_launch_lane_exact_sub(A->lane_params.p, blocks, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit (substitutions): %d", rc);
+    // level 3: k_lane_exact listed the candidates of the substitution class; k_lane_exact_sub (label-aware: k_lane_exact_sub_labeled
+    // behind k_lane_exact_labeled) walks them, a lane each, taking their number from device memory — sized for the most there can
+    // be, its wavefronts leave at once where there are fewer
+    if (LP.exact >= 3u) {
+        if (int rc = mgx_launch_lane_exact_sub(A->lane_params.p, blocks, pl.labeled ? 1 : 0, A->hstream)) return fail(MGX_ERR_NO_DEVICE, "lane kernel, exact exit (substitutions): %d", rc);
     }
     unsigned long long done = 0;
     HIP_TRY(copy_sync(A, &done, cursor(A, CUR_LANE_DONE), 8, hipMemcpyDeviceToHost));      // (synchronises with the kernels)

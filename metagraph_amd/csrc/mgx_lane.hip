@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(64, MGX_LANE_WAVES_PER_SIMD) k_lane(const Lane
 // of its own because k_lane has no register to spare — the same test inside its loop, in front of the DP, made the allocator
 // spill 33 VGPRs in the column loop, a mark tested where k_lane fetches its items cost 25 more spilled SGPRs there — and because
 // this way k_lane is the code it was: it never meets these reads.  One lane per read, in read order.
-// Label-aware batches have a kernel of their own, k_lane_exact_labeled: the same loop around lane_exact_t<true>, whose filter over
+// Label-aware batches have a kernel of their own, k_lane_exact_labeled (and k_lane_exact_sub_labeled behind it at level 3): the same loop around lane_exact_t<true>, whose filter over
 // the seeds' rows and scan over the path's rows (up to ~120 independent 8-byte gathers a read, four in flight at a time) take 30
 // registers more; k_lane_exact, compiled without them, keeps its code and its occupancy for the unlabeled batches.
 template <bool LABELED>
@@ -189,6 +189,25 @@ __device__ __forceinline__ void lane_exact_body(const LaneParams &LP) {
                     LaneSubCand c;
                     c.read = (uint32_t)read; c.strand = (uint32_t)R.strand; c.lo = (uint32_t)run_lo; c.hi = (uint32_t)run_hi;
                     gst(LP.sub_list + p0, c);
+                }
+            }
+        } else {
+            // ... label-aware: for k_lane_exact_sub_labeled, with what the seed filter found (it is not run again there)
+            LV<bool> cv;
+            cv.v = cls == LANE_EXACT_SUB;
+            const uint64_t cm = wave_ballot(cv);
+            if (cm) {
+                LV<uint64_t> pv;
+                pv.v = 0;
+                if (lane == 0) pv.v = atomicAdd(LP.bail_hist + LANE_HIST_SUB_CAND, (unsigned long long)popc64(cm));
+                const uint64_t p0 = wave_bcast(pv, 0) + (uint64_t)popc64(cm & ((1ull << lane) - 1));
+                if (cv.v) {
+                    LaneSubCandLabeled c;
+                    c.read = (uint32_t)read; c.strand = (uint32_t)R.strand; c.lo = (uint32_t)run_lo; c.hi = (uint32_t)run_hi;
+                    c.label = R.label;
+                    c.nm[0] = R.rr.num_matches_fwd; c.nm[1] = R.rr.num_matches_rc; c.ns[0] = R.rr.n_seeds_fwd; c.ns[1] = R.rr.n_seeds_rc;
+                    c.pad[0] = c.pad[1] = c.pad[2] = 0u;
+                    gst((LaneSubCandLabeled *)LP.sub_list + p0, c);
                 }
             }
         }
@@ -286,6 +305,69 @@ __global__ void __launch_bounds__(64) k_lane_exact_sub(const LaneParams *__restr
 }
 __global__ void __launch_bounds__(64) k_lane_exact_labeled(const LaneParams *__restrict__ LPp) { lane_exact_body<true>(*LPp); }
 
+// The substitution class of a label-aware batch, behind k_lane_exact_labeled: k_lane_exact_sub's loop over LaneSubCandLabeled
+// records.  k_lane_exact_labeled has tested the rows of the mapped nodes on both sides of the run (in the pass its path-class reads
+// make anyway), so only candidates whose mapped nodes all carry { L } walk; lane_exact_sub<true>() walks, tests the walked nodes'
+// rows — up to k gathers, four in flight — and the rest.  Nothing is written before every test has passed.
+__global__ void __launch_bounds__(64) k_lane_exact_sub_labeled(const LaneParams *__restrict__ LPp) {
+    const LaneParams &LP = *LPp;
+    __shared__ uint32_t s_walk[LANE_SUB_MAX_WALK][64];
+    const int lane = (int)threadIdx.x;
+    const uint64_t n_cand = (uint64_t)gld(LP.bail_hist + LANE_HIST_SUB_CAND);
+    const LaneSubCandLabeled *list = (const LaneSubCandLabeled *)LP.sub_list;
+    LaneChip chip;
+    chip.lane = lane; chip.qw = nullptr; chip.qstride = 0; chip.cold = &s_walk[0][lane]; chip.cstride = 64;
+    LineCtr lc = { 0, 0, 0 };
+    uint32_t n_done = 0, n_cap = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * 64; base < n_cand; base += (uint64_t)gridDim.x * 64) {
+        const uint64_t at = base + (uint64_t)lane;
+        LaneResult R;
+        R.words = 0;
+        LV<bool> hv;
+        hv.v = false;
+        uint64_t read = 0;
+        if (at < n_cand) {
+            const LaneSubCandLabeled c = gld(list + at);
+            read = c.read;
+            R.label = c.label;
+            R.rr.num_matches_fwd = c.nm[0]; R.rr.num_matches_rc = c.nm[1]; R.rr.n_seeds_fwd = c.ns[0]; R.rr.n_seeds_rc = c.ns[1];
+            hv.v = lane_exact_sub<true>(LP, read, (int)c.strand, (int32_t)c.lo, (int32_t)c.hi, chip.cold, chip.cstride, R, lc);
+        }
+        if (!wave_ballot(hv)) continue;
+        LV<int32_t> wv;
+        wv.v = hv.v ? (int32_t)R.words : 0;
+        const LV<int32_t> pre = wave_prefix_sum_excl(wv);
+        const int32_t total = wave_sum(wv);
+        LV<uint64_t> sv;
+        sv.v = 0;
+        if (lane == 0) sv.v = atomicAdd(LP.P.out_cursor, (unsigned long long)total);
+        const uint64_t so = wave_bcast(sv, 0) + (uint64_t)pre.v;
+        if (hv.v) {
+            lane_emit_t<true, true, true>(LP, read, nullptr, chip, R, so);
+            gst(LP.P.work_key + read, LP.done_key);
+            ++n_done; n_cap += (uint32_t)(R.rr.status != ST_OK);
+        }
+    }
+    LV<int32_t> v;
+    v.v = (int32_t)n_done; const int32_t nd = wave_sum(v);
+    v.v = (int32_t)n_cap; const int32_t nc = wave_sum(v);
+    v.v = (int32_t)(lc.rank_lines + lc.bit_lines); const int32_t rl = wave_sum(v);
+    v.v = (int32_t)lc.select_lines; const int32_t sl = wave_sum(v);
+    if (lane == 0) {
+        if (nd) {
+            atomicAdd(LP.done_count, (unsigned long long)nd);
+            atomicAdd(LP.bail_hist + LANE_HIST_EXACT, (unsigned long long)nd);
+            atomicAdd(LP.bail_hist + LANE_HIST_EXACT_SUB, (unsigned long long)nd);
+        }
+        if (nc) atomicAdd(&LP.P.stats->capacity_errors, (unsigned long long)nc);
+        if (rl | sl) {
+            atomicAdd(&LP.P.stats->rank_lines, (unsigned long long)rl);
+            atomicAdd(&LP.P.stats->select_lines, (unsigned long long)sl);
+            atomicAdd(&LP.P.stats->lane_lines, (unsigned long long)rl + (unsigned long long)sl);
+        }
+    }
+}
+
 // blocks = resident wavefronts (wavefront b owns LaneParams::scratch + b * wave_stride)
 // d_params: the LaneParams of this launch in device memory
 extern "C" int mgx_launch_lane(const void *d_params, uint32_t blocks, void *stream) {
@@ -300,9 +382,11 @@ extern "C" int mgx_launch_lane_exact(const void *d_params, uint32_t blocks, int 
     else k_lane_exact<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     return (int)hipGetLastError();
 }
-// the substitution class, behind mgx_launch_lane_exact on the same stream (LaneParams::exact >= 3, unlabeled batches)
-extern "C" int mgx_launch_lane_exact_sub(const void *d_params, uint32_t blocks, void *stream) {
-    k_lane_exact_sub<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
+// the substitution class, behind mgx_launch_lane_exact on the same stream (LaneParams::exact >= 3)
+// labeled: as mgx_launch_lane_exact
+extern "C" int mgx_launch_lane_exact_sub(const void *d_params, uint32_t blocks, int labeled, void *stream) {
+    if (labeled) k_lane_exact_sub_labeled<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
+    else k_lane_exact_sub<<<blocks, 64, 0, (hipStream_t)stream>>>(static_cast<const LaneParams *>(d_params));
     return (int)hipGetLastError();
 }
 extern "C" int mgx_lane_waves_per_simd(void) { return MGX_LANE_WAVES_PER_SIMD; }

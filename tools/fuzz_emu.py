@@ -6,6 +6,7 @@ CPU only (test infrastructure: the oracle is the checker, the host model runs th
 import argparse
 import os
 import random
+import re
 import sys
 import time
 
@@ -48,6 +49,7 @@ def main():
     n_reads_total = 0
     n_lane_total = 0
     n_exact_total = 0
+    n_sub_total = 0                      # ... of them in the substitution class (MGX_EMU_LANE_EXACT=3)
     sl_why = {}
     lab_hist = [0] * 12                  # --labels: reads by their number of alignments (0..5+), alignments by their number of labels
     while time.time() < t_end and not (args.worlds and it >= args.start + args.worlds):
@@ -254,9 +256,16 @@ def main():
             n_reads_total += len(reads)
             if args.lane:
                 n_lane_total += e.lane_stats()[1]
-                if os.environ.get("MGX_EMU_LANE_EXACT") in ("1", "2") and e.lane_stats()[0] and all(st == 0 for st in status):
+                if os.environ.get("MGX_EMU_LANE_EXACT") in ("1", "2", "3") and e.lane_stats()[0] and all(st == 0 for st in status):
                     # (the exact exit: an alignment and no extension)
                     n_exact_total += sum(1 for q, x in enumerate(e.seed_info()) if got[q] and x["n_extensions"] == 0)
+                    # (level 3: those with a mismatch are the substitution class — "p= 1X (L-1-p)=", p >= k, one alignment)
+                    for q, x in enumerate(e.seed_info()):
+                        if got[q] and x["n_extensions"] == 0 and "X" in got[q][0]["cigar"]:
+                            mt = re.fullmatch(r"(\d+)=1X(?:(\d+)=)?", got[q][0]["cigar"])
+                            assert os.environ.get("MGX_EMU_LANE_EXACT") == "3" and len(got[q]) == 1 and mt and int(mt.group(1)) >= k \
+                                and int(mt.group(1)) + 1 + int(mt.group(2) or 0) == len(reads[q]), ("substitution class", q, reads[q], got[q])
+                            n_sub_total += 1
             if args.seedlane:
                 ran, done, why = e.seedlane_stats()
                 n_lane_total += done
@@ -266,7 +275,7 @@ def main():
             print("MISMATCH", desc)
             print(str(ex)[:3000])
             sys.exit(1)
-    print("ok: %d worlds, %d reads, no difference" % (it, n_reads_total) + (" (%d reads finished by the lane path%s)" % (n_lane_total, ", %d of them through the exact exit" % n_exact_total if os.environ.get("MGX_EMU_LANE_EXACT") in ("1", "2") else "") if args.lane else "")
+    print("ok: %d worlds, %d reads, no difference" % (it, n_reads_total) + (" (%d reads finished by the lane path%s)" % (n_lane_total, ", %d of them through the exact exit, %d of those with one substitution" % (n_exact_total, n_sub_total) if os.environ.get("MGX_EMU_LANE_EXACT") in ("1", "2", "3") else "") if args.lane else "")
           + (" (%d reads seeded by the lane-per-read seeder; left by reason: %s)" % (n_lane_total, dict(sorted(sl_why.items()))) if args.seedlane else "")
           + (" (reads with 0..5+ alignments: %s; alignments with 0..5+ labels: %s)" % (lab_hist[:6], lab_hist[6:]) if args.labels else ""))
 
